@@ -33,11 +33,11 @@ def _mix(z):
     return z ^ (z >> np.uint64(31))
 
 
-def raw(seed, stream, n):
-    """The n uint64 draws of stream `stream` of `seed`."""
+def raw(seed, stream, n, start=0):
+    """The n uint64 draws of stream `stream` of `seed` that follow its first `start`."""
     with np.errstate(over="ignore"):
         st = _mix(np.uint64(seed) ^ (_STREAM * np.uint64(stream + 1)))
-        idx = np.arange(1, n + 1, dtype=np.uint64)
+        idx = np.arange(start + 1, start + n + 1, dtype=np.uint64)
         return _mix(st + idx * _GAMMA)
 
 
@@ -53,10 +53,11 @@ def bf16_bits_to_f32(b):
     return (np.asarray(b, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
-def fill(dtype, seed, stream, n):
-    """numpy array of n elements of ftar dtype `dtype` (id or name)."""
+def fill(dtype, seed, stream, n, start=0):
+    """numpy array of n elements of ftar dtype `dtype` (id or name): elements start .. start + n - 1 of the
+    stream, so a long array can be filled piece by piece."""
     dt = BY_NAME[dtype] if isinstance(dtype, str) else dtype
-    z = raw(seed, stream, n)
+    z = raw(seed, stream, n, start)
     if dt in (0, 1):
         return (z & np.uint64(0xFF)).astype(np.uint8).view(DTYPES[dt][1])
     if dt in (2, 3):

@@ -15,6 +15,11 @@
 
 Prints ONE JSON line on rank 0.  Inputs are synthetic (splitmix64 fp32 in
 [-1, 1) at N=1, torch.rand at N>1) and resident in HBM before timing starts.
+
+At N = 1 a plain run sets up, warms up, times --steps steps and prints the
+line; --dump-outputs DIR also writes the last timed step's result.  The other
+line items of N = 1 (same_buffers, the spot check, k8 / --sweep, engine_local,
+host_local, cpu_baseline) run only with --full.
 """
 import argparse
 import json
@@ -37,6 +42,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="N=1: after the headline also run the same-buffers loop, the bit-exact spot check, the k = 8 "
+                         "item (k = 1..16 with --sweep), engine_local, host_local and the CPU baseline (each with its "
+                         "own --no-... switch); a run without --full does the headline alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="N=1: write what the last timed step computed (its destination bucket; a fixed sample of "
+                         "one larger than 64 MB) as DIR/<name>.npy, float32 or float64")
     ap.add_argument("--sources", dest="k", type=int, default=2, help="N=1: number of source buckets k")
     ap.add_argument("--elements", dest="n", type=int, default=0, help="elements per bucket (default 2^26 at N=1, 2^28 at N>1)")
     ap.add_argument("--dtype", default="f32")
@@ -47,7 +59,7 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="N=1: CPU baseline sample length")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-peer", action="store_true", help="N>1: leave the peer-direct forms out of the sweep")
-    ap.add_argument("--sweep", action="store_true", help="N=1: also report k=1..16 (vector_add.cu:182)")
+    ap.add_argument("--sweep", action="store_true", help="N=1, with --full: also report k=1..16 (vector_add.cu:182)")
     ap.add_argument("--no-engine-local", action="store_true",
                     help="N=1: skip the engine_local line item (P = 8 in-process ranks on this GPU at the C4 bucket)")
     ap.add_argument("--no-host-local", action="store_true",
@@ -192,12 +204,67 @@ def cpu_baseline(k, n, seconds):
             "sample": f"oracle reduce k={k} n={m} fp32 single thread, best of {iters}"}
 
 
+def fill_bucket(fi, dtype, seed, stream, n, piece=1 << 22):
+    """fi.fill(dtype, seed, stream, n), generated piece by piece on the CPUs this process may use (16 at the
+    most): the same values, in a fraction of the time one pass over 2^26 elements takes."""
+    import numpy as np
+    from concurrent.futures import ThreadPoolExecutor
+    out = np.empty(n, fi.np_dtype(dtype))
+
+    def work(lo):
+        hi = min(n, lo + piece)
+        out[lo:hi] = fi.fill(dtype, seed, stream, hi - lo, start=lo)
+    with ThreadPoolExecutor(max(1, min(16, int(host_cores()["available_cpus"])))) as ex:
+        list(ex.map(work, range(0, n, piece)))
+    return out
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000   # --dump-outputs writes no more than this in all
+DUMP_EDGE, DUMP_INNER = 1 << 20, 1 << 22
+
+
+def as_float(fi, dtype, x):
+    """A bucket's elements as float32 (float64 where float32 cannot hold the type's values)."""
+    import numpy as np
+    if dtype == "bf16":
+        return fi.bf16_bits_to_f32(x)
+    return x.astype(np.float64 if dtype in ("f64", "i32", "i64") else np.float32, copy=False)
+
+
+def dump_sample(x):
+    """x itself if it fits DUMP_MAX_BYTES, else a fixed sample of it: its first and last DUMP_EDGE elements
+    and DUMP_INNER more at seeded indices in ascending order -- the same elements in every run."""
+    import numpy as np
+    if x.nbytes <= DUMP_MAX_BYTES:
+        return x, "all"
+    inner = np.sort(np.random.default_rng(0xD0E5).integers(0, x.size, DUMP_INNER))
+    idx = np.concatenate([np.arange(DUMP_EDGE), inner, np.arange(x.size - DUMP_EDGE, x.size)])
+    return x[idx], (f"first {DUMP_EDGE}, {DUMP_INNER} at indices numpy's default_rng(0xD0E5).integers(0, "
+                    f"{x.size}) draws, sorted, last {DUMP_EDGE}")
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: float array} as dirname/<name>.npy (dump_sample of each); returns what was written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    done, total = {}, 0
+    for name, x in arrays.items():
+        y, what = dump_sample(x)
+        y = np.ascontiguousarray(y)
+        total += y.nbytes
+        assert total <= DUMP_MAX_BYTES, (name, total)
+        np.save(os.path.join(dirname, name + ".npy"), y)
+        done[name] = {"dtype": str(y.dtype), "elements": int(y.size), "of": int(x.size), "sample": what}
+    return done
+
+
 def bench_single(a):
     """N = 1: the k-way reduce kernel on `sets` disjoint (k sources + destination) buffer sets, one step per
     set in rotation, so every launch streams data the previous launches did not leave in the 256 MB
     Infinity Cache (MALL): the AllReduce's regime, where every piece is new data.  The same-buffer loop of
     the reference harness (vector_add.cu:110-140) is reported next to it as `same_buffers`: there the MALL
-    absorbs part of the rewritten destination and the rate overstates HBM."""
+    absorbs part of the rewritten destination and the rate overstates HBM.  That loop and every
+    other line item run only with --full; without it the run is the headline's set-up, warm-up and timed steps."""
     import numpy as np
     import torch
 
@@ -214,10 +281,11 @@ def bench_single(a):
     for i in range(sets):
         ss, heads, tails = [], [], []
         for j in range(k):
-            x = fi.fill(a.dtype, 0x5EED + i, j, n)
+            x = fill_bucket(fi, a.dtype, 0x5EED + i, j, n)
             ss.append(torch.from_numpy(x.view(np.uint8)).to(dev))
-            heads.append(x[:m].copy())
-            tails.append(x[n - m:].copy())
+            if a.full:
+                heads.append(x[:m].copy())
+                tails.append(x[n - m:].copy())
             del x
         srcs.append(ss)
         dsts.append(torch.empty(n * esz, dtype=torch.uint8, device=dev))
@@ -243,29 +311,39 @@ def bench_single(a):
 
     ms, wall = run(a.steps, a.warmup, rotate=True)
     kernel = ftar.last_kernel()   # the kernel those launches ran (the PMC traffic must be this one's)
-    ms_same, _ = run(a.steps, a.warmup, rotate=False)
+    dumped = None
+    if a.dump_outputs:   # the last timed step's destination (copies only: the kernel order of a trace stays)
+        last = dsts[(a.steps - 1) % sets].cpu().numpy().view(fi.np_dtype(a.dtype))
+        dumped = dump_outputs(a.dump_outputs, {"reduce_out": as_float(fi, a.dtype, last)})
+        del last
     algo_bytes = (k + 1) * n * esz
     gbps = algo_bytes / (ms * 1e-3) / 1e9
-    gbps_same = algo_bytes / (ms_same * 1e-3) / 1e9
-    for i in range(sets):   # every set's destination holds its last reduce
-        step(i)
-    torch.cuda.synchronize()
+    check, same = "not run (--full)", None
+    if a.full:
+        ms_same, _ = run(a.steps, a.warmup, rotate=False)
+        gbps_same = algo_bytes / (ms_same * 1e-3) / 1e9
+        same = {"GBps": round(gbps_same, 2), "ms_per_step": round(ms_same, 5),
+                "note": "every step on set 0 (the reference harness's loop); the Infinity Cache absorbs "
+                        "part of the rewritten destination, so this overstates HBM"}
+        for i in range(sets):   # every set's destination holds its last reduce
+            step(i)
+        torch.cuda.synchronize()
 
-    # spot check of every set (first and last 64 Ki elements): numpy's fp32 adds, folded left to right
-    # like reduce_sum (mpi_mod.hpp:856-863), must match bit for bit
-    check = "skipped"
-    if a.dtype == "f32":
-        ok = True
-        for i in range(sets):
-            got = dsts[i].view(torch.float32)
-            for part, lo in ((0, 0), (1, n - m)):
-                parts = probes[i][part]
-                exp = parts[0].copy()
-                for h in parts[1:]:
-                    exp = (exp + h).astype(np.float32)
-                g = got[lo:lo + m].cpu().numpy()
-                ok &= bool(np.array_equal(g.view(np.uint32), exp.view(np.uint32)))
-        check = "bit-exact" if ok else "MISMATCH"
+        # spot check of every set (first and last 64 Ki elements): numpy's fp32 adds, folded left to right
+        # like reduce_sum (mpi_mod.hpp:856-863), must match bit for bit
+        check = "skipped"
+        if a.dtype == "f32":
+            ok = True
+            for i in range(sets):
+                got = dsts[i].view(torch.float32)
+                for part, lo in ((0, 0), (1, n - m)):
+                    parts = probes[i][part]
+                    exp = parts[0].copy()
+                    for h in parts[1:]:
+                        exp = (exp + h).astype(np.float32)
+                    g = got[lo:lo + m].cpu().numpy()
+                    ok &= bool(np.array_equal(g.view(np.uint32), exp.view(np.uint32)))
+            check = "bit-exact" if ok else "MISMATCH"
 
     workload = f"reduce_k{k}_{a.dtype}_n{n}"
     traffic, prov = pmc_traffic(workload, kernel)
@@ -280,11 +358,14 @@ def bench_single(a):
         "roofline": {"bound": "hbm", "achieved": round(gbps, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": round(gbps / HBM_PEAK_GBPS, 4), "traffic": traffic, "kernel": kernel,
                      "kernel_sources_sha": kernel_source_digest(), **prov},
-        "same_buffers": {"GBps": round(gbps_same, 2), "ms_per_step": round(ms_same, 5),
-                         "note": "every step on set 0 (the reference harness's loop); the Infinity Cache absorbs "
-                                 "part of the rewritten destination, so this overstates HBM"},
         "check": check, "wall_s": round(wall, 4),
     }
+    if dumped:
+        res["outputs"] = dumped
+    if not a.full:
+        print(json.dumps(res), flush=True)
+        return
+    res["same_buffers"] = same
     # vector_add.cu:182: k = 1..16 with --sweep; by default k = 8 only (k in {2, 8}); two sets in
     # rotation (each (k+1) x 256 MiB >> the MALL)
     sweep = {}
@@ -1978,10 +2059,17 @@ def bench_distributed(a):
 
 def main():
     a = parse()
+    dist = int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.force_dist
+    if a.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
+    if a.dump_outputs and (dist or a.engine_local_only):
+        sys.exit("bench.py: --dump-outputs writes the N = 1 headline's outputs only")
+    if a.sweep and not (a.full or dist):
+        sys.exit("bench.py: --sweep is one of --full's line items: pass --full too")
     if a.engine_local_only:   # one line item alone (under rocprofv3: the engine's kernel timeline)
         print(json.dumps({"engine_local": engine_local(steps=a.steps, warmup=a.warmup,
                                                        chunk_bytes=a.chunk_bytes or None)}), flush=True)
-    elif int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.force_dist:
+    elif dist:
         bench_distributed(a)
     else:
         bench_single(a)

@@ -525,3 +525,50 @@ def test_n_gt_1_stage_order_and_budget_with_synthetic_stage_times():
     # a rehearsal's small budget scales the reserves down: at its start every stage still fits
     clock = bench.StageClock(100.0, 0.0, now=_FakeTime())
     assert bench.run_stage_plan(clock, {n: (lambda lim: None) for n in names}) == names
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f64", "i32", "u8", "bool"])
+@pytest.mark.parametrize("n,piece", [(1, 64), (4099, 4099), (100003, 4096), (8192, 4096)])
+def test_fill_bucket_is_fill(dtype, n, piece):
+    """The N = 1 inputs generated piece by piece on several threads are fi.fill's, element for element (pieces
+    that divide n, that do not, one piece, one element)."""
+    import numpy as np
+    import bench
+    from ftar import inputs as fi
+    got, exp = bench.fill_bucket(fi, dtype, 0x5EED, 1, n, piece=piece), fi.fill(dtype, 0x5EED, 1, n)
+    assert got.dtype == exp.dtype and np.array_equal(got.view(np.uint8), exp.view(np.uint8))
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: a bucket within the 64 MB limit is written whole; a larger one as the same sample in every
+    run (its first and last 2^20 elements and 2^22 seeded ones in between), float32, under the limit."""
+    import numpy as np
+    import bench
+    small = np.arange(1000, dtype=np.float32)
+    d = bench.dump_outputs(str(tmp_path / "a"), {"x": small})
+    assert d["x"]["sample"] == "all" and np.array_equal(np.load(tmp_path / "a" / "x.npy"), small)
+    n = (bench.DUMP_MAX_BYTES // 4) + 12345
+    big = np.arange(n, dtype=np.float32)   # every value below 2^24: exact, so the values are the indices
+    bench.dump_outputs(str(tmp_path / "b"), {"x": big})
+    bench.dump_outputs(str(tmp_path / "c"), {"x": big})
+    b, c = np.load(tmp_path / "b" / "x.npy"), np.load(tmp_path / "c" / "x.npy")
+    assert b.dtype == np.float32 and b.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(b, c)
+    e = bench.DUMP_EDGE
+    assert b.size == 2 * e + bench.DUMP_INNER
+    assert np.array_equal(b[:e], big[:e]) and np.array_equal(b[-e:], big[-e:])
+    assert bool((np.diff(b[e:-e]) >= 0).all()) and 0 <= b[e] and b[-e - 1] < n
+
+
+@pytest.mark.parametrize("dtype,exp", [("f32", "float32"), ("bf16", "float32"), ("f64", "float64"), ("i64", "float64"),
+                                       ("i32", "float64"), ("u16", "float32")])
+def test_dumped_dtype_holds_the_values(dtype, exp):
+    import numpy as np
+    import bench
+    from ftar import inputs as fi
+    x = fi.fill(dtype, 3, 0, 257)
+    y = bench.as_float(fi, dtype, x)
+    assert str(y.dtype) == exp
+    if dtype == "bf16":
+        assert np.array_equal(fi.f32_to_bf16_bits(y), x)
+    elif dtype != "i64":   # float64 holds 53 bits of an int64
+        assert np.array_equal(y.astype(x.dtype), x)

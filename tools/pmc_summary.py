@@ -3,7 +3,7 @@
 
     python tools/pmc_summary.py FETCH_CSV WRITE_CSV [--elements N] [--k 2,8] [--meta META_JSON] [--source DIR]
 
-One entry per k (bench.py launches the k = 2 headline and the k = 8 line item in the same process); entries
+One entry per k (bench.py --full launches the k = 2 headline and the k = 8 line item in the same process); entries
 of other workloads already in the summary are kept.  Every entry names the kernel it measured (its template
 id, as bench.py's roofline reports the kernel it timed), the sha of the kernel sources and the commit of the
 tree the passes ran on (META_JSON, written on the GPU box by tools/gpu_run.sh final): bench.py reports the

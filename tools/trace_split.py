@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a rocprofv3 kernel trace of `python bench.py` (N = 1) into the bench's launch phases.
+"""Split a rocprofv3 kernel trace of `python bench.py --full` (N = 1) into the bench's launch phases.
 
     python tools/trace_split.py run_kernel_trace.csv [--steps 20 --warmup 5 --sets 4] [--out summary.json]
 
