@@ -140,6 +140,10 @@ extern "C" ftar_status_t ftar_debug_reduce_variant(int variant, int dtype, const
   // 200 + bf16 / 300 + bf16 for the flat and hop folds with the integer RNE; dropped to keep build time.)
   else if (dtype == 100 + FTAR_BFLOAT16 && count % 8 == 0)
     e = ftar::hop_variant(variant, srcs, k, dst, count / 8, s);
+  // (The A/B of the 2-byte MAX traits, profiles/f16_minmax/kbench_2byte_max.log, also built the shape sweep
+  // (variants 40-62, k = 2 and 8) for fp16 SUM, u16 SUM, 200 + f16 / 200 + i16 = MAX, and 300 + f16 = fp16 MAX by
+  // integer keys (sign-magnitude flipped to two's complement per packed half, v_pk_max_i16, NaN lanes collected
+  // apart); dropped to keep build time.)
   else return FTAR_ERR_INVALID_ARG;
   return e == hipSuccess ? FTAR_SUCCESS : FTAR_ERR_HIP;
 }
@@ -192,6 +196,115 @@ extern "C" ftar_status_t ftar_debug_bf16_cvt_check(unsigned long long* mismatche
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(mismatches, d_bad, sizeof *d_bad, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(first, d_first, sizeof *d_first, hipMemcpyDeviceToHost) != hipSuccess)
+      st = FTAR_ERR_HIP;
+  }
+  ftar::hip_ignore(hipFree(d_bad));
+  ftar::hip_ignore(hipFree(d_first));
+  return st;
+}
+
+namespace ftar {
+namespace {
+// fp32 -> binary16 round-to-nearest-even in integer arithmetic: overflow to inf, gradual underflow, NaN
+// to a quiet NaN of the same sign (which NaN is outside the contract: the check compares NaN-ness)
+__host__ __device__ constexpr unsigned f16_rne_bits(unsigned u) {
+  const unsigned sign = (u >> 16) & 0x8000u, a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return sign | 0x7e00u;
+  if (a >= 0x47800000u) return sign | 0x7c00u;  // |x| >= 65536 (or inf)
+  if (a >= 0x38800000u) {                       // |x| >= 2^-14: a normal half, unless the rounding carries to inf
+    const unsigned r = a - 0x38000000u;         // exponent rebias 127 -> 15
+    return sign | ((r + 0xfffu + ((r >> 13) & 1u)) >> 13);  // a carry out of the mantissa bumps the exponent
+  }
+  const unsigned e = a >> 23, m = (a & 0x7fffffu) | 0x800000u;  // value = m x 2^(e - 150), half ulp = 2^-24
+  const unsigned shift = 126u - e;                              // e <= 112: shift >= 14
+  if (e == 0 || shift > 24u) return sign;  // below 2^-25 (fp32 subnormals included): rounds to zero
+  const unsigned h = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  return sign | (h + ((rem > half || (rem == half && (h & 1u))) ? 1u : 0u));
+}
+// binary16 -> fp32 by integer expansion (exact)
+__host__ __device__ constexpr unsigned f16_widen_bits(unsigned h) {
+  const unsigned sign = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 0x3ffu;
+  if (e == 31u) return sign | 0x7f800000u | (m << 13);
+  if (e) return sign | ((e + 112u) << 23) | (m << 13);
+  if (!m) return sign;
+  int p = 9;  // the leading one of a subnormal: value = m x 2^-24 = 2^(p - 24) x (m / 2^p)
+  while (!((m >> p) & 1u)) --p;
+  return sign | ((unsigned)(p + 103) << 23) | ((m << (23 - p)) & 0x7fffffu);
+}
+static_assert(f16_rne_bits(0x3f800000u) == 0x3c00u && f16_rne_bits(0x477ff000u) == 0x7c00u &&
+              f16_rne_bits(0x477fefffu) == 0x7bffu && f16_rne_bits(0x33000000u) == 0u &&
+              f16_rne_bits(0x33000001u) == 1u && f16_rne_bits(0x33c00000u) == 2u && f16_rne_bits(0xb8800000u) == 0x8400u &&
+              f16_rne_bits(0x387fffffu) == 0x0400u && f16_rne_bits(0x3f801000u) == 0x3c00u &&
+              f16_rne_bits(0x3f803000u) == 0x3c02u);
+static_assert(f16_widen_bits(0x3c00u) == 0x3f800000u && f16_widen_bits(1u) == 0x33800000u &&
+              f16_widen_bits(0x83ffu) == 0xb87fc000u && f16_widen_bits(0xfc00u) == 0xff800000u);
+
+__device__ __forceinline__ bool f16_bits_differ(unsigned got, unsigned want) {  // 16-bit patterns
+  const bool ng = (got & 0x7fffu) > 0x7c00u, nw = (want & 0x7fffu) > 0x7c00u;
+  return ng != nw || (!nw && got != want);
+}
+// every float bit pattern u (lo half) and u ^ 0x80000001 (hi half) through the production packing
+// (pack_f16: the v_fin of the fp16 traits) and the scalar narrowing (their s_fin) against the integer RNE
+__global__ void __launch_bounds__(256) f16_narrow_check_kernel(unsigned long long* bad, unsigned* first) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+  unsigned long long mine = 0;
+  unsigned first_mine = 0xffffffffu;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < (1ull << 32); i += stride) {
+    const unsigned u = (unsigned)i, v = u ^ 0x80000001u;
+    const unsigned got = pack_f16(__uint_as_float(u), __uint_as_float(v));
+    const unsigned one = HalfFmt::narrow(__uint_as_float(u));
+    if (f16_bits_differ(got & 0xffffu, f16_rne_bits(u)) || f16_bits_differ(got >> 16, f16_rne_bits(v)) ||
+        f16_bits_differ(one, f16_rne_bits(u))) {
+      ++mine;
+      first_mine = first_mine < u ? first_mine : u;
+    }
+  }
+  if (mine) {
+    atomicAdd(bad, mine);
+    atomicMin(first, first_mine);
+  }
+}
+// every half bit pattern h (lo) and h ^ 0x8001 (hi) through the production widening (unpack_f16: the
+// v_init of the fp16 traits; HalfFmt::widen: their s_init) against the integer expansion
+__global__ void __launch_bounds__(256) f16_widen_check_kernel(unsigned long long* bad, unsigned* first) {
+  const unsigned h = blockIdx.x * 256 + threadIdx.x, g = h ^ 0x8001u;
+  if (h >= 0x10000u) return;
+  const f32x2 w = unpack_f16(h | (g << 16));
+  auto differ = [](float got, unsigned want) {
+    const unsigned gb = __float_as_uint(got);
+    const bool ng = (gb & 0x7fffffffu) > 0x7f800000u, nw = (want & 0x7fffffffu) > 0x7f800000u;
+    return ng != nw || (!nw && gb != want);
+  };
+  if (differ(w.x, f16_widen_bits(h)) || differ(w.y, f16_widen_bits(g)) ||
+      differ(HalfFmt::widen((unsigned short)h), f16_widen_bits(h))) {
+    atomicAdd(bad, 1ull);
+    atomicMin(first, h);
+  }
+}
+}  // namespace
+}  // namespace ftar
+
+// Test hook (not in ftar.h), the sibling of ftar_debug_bf16_cvt_check: mismatches[0] = how many of the 2^32
+// float bit patterns the production fp32 -> fp16 conversion (v_cvt_pk_f16_f32, and the scalar one of the
+// element-wise paths) rounds differently from an integer round-to-nearest-even; mismatches[1] = how many of
+// the 2^16 half bit patterns widen differently from an integer expansion; first[0..1] = the first such
+// pattern of each direction (0xffffffff: none).  NaNs compare as NaN or not.
+extern "C" ftar_status_t ftar_debug_f16_cvt_check(unsigned long long* mismatches, unsigned* first) {
+  if (!mismatches || !first) return FTAR_ERR_INVALID_ARG;
+  unsigned long long* d_bad = nullptr;
+  unsigned* d_first = nullptr;
+  ftar_status_t st = FTAR_SUCCESS;  // both buffers are freed on every path below
+  if (hipMalloc(&d_bad, 2 * sizeof *d_bad) != hipSuccess || hipMalloc(&d_first, 2 * sizeof *d_first) != hipSuccess)
+    st = FTAR_ERR_NO_MEMORY;
+  if (st == FTAR_SUCCESS && (hipMemset(d_bad, 0, 2 * sizeof *d_bad) != hipSuccess ||
+                             hipMemset(d_first, 0xff, 2 * sizeof *d_first) != hipSuccess))
+    st = FTAR_ERR_HIP;
+  if (st == FTAR_SUCCESS) {
+    hipLaunchKernelGGL(ftar::f16_narrow_check_kernel, dim3(8192), dim3(256), 0, nullptr, d_bad, d_first);
+    hipLaunchKernelGGL(ftar::f16_widen_check_kernel, dim3(256), dim3(256), 0, nullptr, d_bad + 1, d_first + 1);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(mismatches, d_bad, 2 * sizeof *d_bad, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(first, d_first, 2 * sizeof *d_first, hipMemcpyDeviceToHost) != hipSuccess)
       st = FTAR_ERR_HIP;
   }
   ftar::hip_ignore(hipFree(d_bad));

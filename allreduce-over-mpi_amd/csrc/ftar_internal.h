@@ -118,7 +118,7 @@ struct ReduceItem {
   size_t off;                   // element offset of the block in dst
   size_t len;                   // elements (> 0)
   std::vector<Operand> srcs;    // fold order: dst = ((srcs[0] OP srcs[1]) OP srcs[2]) ...
-  bool round_each = false;      // bf16: round after every add (one hop per add)
+  bool round_each = false;      // bf16, fp16: round after every add (one hop per add)
   std::vector<int> shape;       // nested fold of srcs (launch_reduce); empty = flat
 };
 
@@ -154,11 +154,12 @@ ftar_status_t check_world(const Topology& t, int nranks, size_t count, Form form
 // reduce kernels (reduce_impl.h; dispatch in reduce_kernels.hip)
 // ---------------------------------------------------------------------------
 // srcs: host array of k device pointers. k == 1 copies.
-// round_each: bf16 sums round to bf16 after every add (no effect on other dtypes).
+// round_each: bf16 and fp16 sums round to their format after every add (no effect
+// on other dtypes or ops).
 // shape: bottom-up widths of a nested fold (srcs in depth-first leaf order,
-// product == k, at most kMaxFoldLevels levels; bf16 inner nodes rounded);
-// nlevels <= 1 = flat.  Only float sums depend on it: integer sums and AND are
-// associative and take the flat kernel.
+// product == k, at most kMaxFoldLevels levels; bf16 and fp16 inner nodes rounded);
+// nlevels <= 1 = flat.  Only float sums depend on it: integer sums, AND, MAX and
+// MIN are associative and take the flat kernel.
 constexpr int kMaxFoldLevels = 4;
 ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
                             hipStream_t stream, bool round_each = false, const int* shape = nullptr,

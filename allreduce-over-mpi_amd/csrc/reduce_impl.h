@@ -8,7 +8,7 @@
 // Design (bandwidth-bound: (k+1)*n*sizeof(T) bytes, ~0 flops per byte, no MFMA):
 //   * 16 B per lane per access, one wave instruction = 1 KiB contiguous per
 //     source: fully coalesced;
-//   * k = 2..16 for fp32/bf16, k = 2..8 for the other types: reduce_lds_kernel stages
+//   * k = 2..16 for fp32/bf16/fp16, k = 2..8 for the other types: reduce_lds_kernel stages
 //     U tiles of every source per wave through LDS with LDS-DMA
 //     (global_load_lds_dwordx4, nontemporal) and folds tile by tile as each
 //     tile lands (counted vmcnt); stores are nontemporal too (cold data: every
@@ -26,7 +26,10 @@
 //   * arithmetic follows the reference's C++ semantics bit for bit:
 //       float/double in their own precision (no FMA: pure adds),
 //       narrow integers wrap (promotion + truncating store == modular add),
-//       bool sum = OR of non-zero, bf16 (extension) = fp32 accumulate + one RNE.
+//       bool sum = OR of non-zero;
+//   * extensions (no reference): bf16 and fp16 sums = fp32 accumulate + one RNE per
+//     reduce; MAX / MIN = signed or unsigned integer compare, IEEE 754-2019
+//     maximum / minimum on floats (exact: every fold order gives the same bits).
 #pragma once
 // Internal: the reduce kernels, their traits and launchers, included by reduce_kernels.hip (the
 // production dispatch, libftar.so) and bench_kernels.hip (the A/B harness, libftar_bench.so);
@@ -86,6 +89,11 @@ constexpr bool kNtLoads = true, kNtStores = true;
 // profiles/r02/kbench_cold_small_wg.log, kbench_k2_shape_ab.log): for 4-byte
 // k = 2, U = 1 x W = 2 (4 KiB of LDS, up to 16 workgroups per CU) measured
 // +0.6 / +1.3 / +1.8 % over U = 4 x W = 4 in three runs; elsewhere the table held.
+// The fp16 sum and the MAX / MIN traits take the shapes of the sums of their width.  The 2-byte MAX / MIN on
+// packed instructions (fp16, i16, u16: one VALU op per dword and source) run 0.5-1 % under the 2-byte sums at
+// k = 8, at the rate of the 4-byte folds that are as light; a sweep of these shapes for them and an
+// integer-key formulation gave no gain that held through the production dispatch (DESIGN §4,
+// profiles/f16_minmax/).
 template <class Tr, int K>
 constexpr int kLdsTiles = sizeof(typename Tr::S) >= 4 ? (K == 2 ? 1 : K <= 4 ? 3 : K <= 6 ? 2 : K <= 10 ? 4 : 2)
                                                      : (K <= 4 ? 4 : K == 5 ? 2 : K == 6 ? 5 : K <= 10 ? 4 : 2);
@@ -164,16 +172,22 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
   if constexpr (HW) return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
   else return (bf16_round_bits(lo) >> 16) | bf16_round_bits(hi);
 }
+// IEEE binary16 <-> fp32 through the compiler's conversions: v_cvt_f32_f16 (exact, subnormals included)
+// and, two floats at once, v_cvt_pk_f16_f32 (RNE: overflow to inf, gradual underflow).  Both directions
+// are checked over every bit pattern against integer code (ftar_debug_f16_cvt_check).
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pack_f16(float lo, float hi) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, f16x2));
+}
+__device__ __forceinline__ f32x2 unpack_f16(unsigned x) {
+  return __builtin_convertvector(__builtin_bit_cast(f16x2, x), f32x2);
+}
+// The two 16-bit float formats as the sum traits below see them: widen one element / a pair of packed
+// words, pack two floats (one RNE each), round a float to the format and back (rnd, rnd4).
 template <bool HW>
-struct BF16SumT {
-  using S = unsigned short;
-  using SA = float;
-  struct VA {
-    f32x4 lo, hi;
-  };
-  __device__ static SA s_init(S x) { return bf16_to_f32(x); }
-  __device__ static SA s_comb(SA a, S x) { return a + bf16_to_f32(x); }
-  __device__ static S s_fin(SA a) { return f32_to_bf16(a); }
+struct Bf16Fmt {
+  __device__ static float widen(unsigned short h) { return bf16_to_f32(h); }
+  __device__ static unsigned short narrow(float f) { return f32_to_bf16(f); }
   __device__ static f32x4 unpack(unsigned a, unsigned b) {
     f32x4 r;
     r.x = __uint_as_float(a << 16);
@@ -182,40 +196,63 @@ struct BF16SumT {
     r.w = __uint_as_float(b & 0xffff0000u);
     return r;
   }
-  __device__ static VA v_init(u32x4 x) { return {unpack(x.x, x.y), unpack(x.z, x.w)}; }
-  __device__ static VA v_comb(VA a, u32x4 x) {
-    VA b = v_init(x);
-    return {a.lo + b.lo, a.hi + b.hi};
-  }
   __device__ static unsigned pack(float lo, float hi) { return pack_bf16<HW>(lo, hi); }
-  __device__ static u32x4 v_fin(VA a) {
-    return u32x4{pack(a.lo.x, a.lo.y), pack(a.lo.z, a.lo.w), pack(a.hi.x, a.hi.y), pack(a.hi.z, a.hi.w)};
-  }
-  // nested folds: an inner node's value is stored as bf16 by the staged
-  // schedule, so it is rounded before its parent adds it
   __device__ static float rnd(float f) { return __uint_as_float(bf16_round_bits(f)); }
   __device__ static f32x4 rnd4(f32x4 v) {
     if constexpr (HW) return unpack(pack(v.x, v.y), pack(v.z, v.w));
     else return f32x4{rnd(v.x), rnd(v.y), rnd(v.z), rnd(v.w)};
   }
-  __device__ static SA s_add(SA a, SA b) { return a + b; }
-  __device__ static SA s_rnd(SA a) { return rnd(a); }
-  __device__ static VA v_add(VA a, VA b) { return {a.lo + b.lo, a.hi + b.hi}; }
-  __device__ static VA v_rnd(VA a) { return {rnd4(a.lo), rnd4(a.hi)}; }
 };
-// bf16 folded hop by hop: every add rounds to bf16 (the one-round ring fold has
+struct HalfFmt {
+  __device__ static float widen(unsigned short h) { return (float)__builtin_bit_cast(_Float16, h); }
+  __device__ static unsigned short narrow(float f) { return __builtin_bit_cast(unsigned short, (_Float16)f); }
+  __device__ static f32x4 unpack(unsigned a, unsigned b) {
+    const f32x2 lo = unpack_f16(a), hi = unpack_f16(b);
+    return f32x4{lo.x, lo.y, hi.x, hi.y};
+  }
+  __device__ static unsigned pack(float lo, float hi) { return pack_f16(lo, hi); }
+  __device__ static float rnd(float f) { return (float)(_Float16)f; }
+  __device__ static f32x4 rnd4(f32x4 v) { return unpack(pack(v.x, v.y), pack(v.z, v.w)); }
+};
+// 16-bit float sums (extensions): fp32 accumulate, one RNE to the format per reduce call
+template <class F>
+struct H16SumT {
+  using S = unsigned short;
+  using SA = float;
+  struct VA {
+    f32x4 lo, hi;
+  };
+  __device__ static SA s_init(S x) { return F::widen(x); }
+  __device__ static SA s_comb(SA a, S x) { return a + F::widen(x); }
+  __device__ static S s_fin(SA a) { return F::narrow(a); }
+  __device__ static VA v_init(u32x4 x) { return {F::unpack(x.x, x.y), F::unpack(x.z, x.w)}; }
+  __device__ static VA v_comb(VA a, u32x4 x) {
+    VA b = v_init(x);
+    return {a.lo + b.lo, a.hi + b.hi};
+  }
+  __device__ static u32x4 v_fin(VA a) {
+    return u32x4{F::pack(a.lo.x, a.lo.y), F::pack(a.lo.z, a.lo.w), F::pack(a.hi.x, a.hi.y), F::pack(a.hi.z, a.hi.w)};
+  }
+  // nested folds: an inner node's value is stored in the 16-bit format by the
+  // staged schedule, so it is rounded before its parent adds it
+  __device__ static SA s_add(SA a, SA b) { return a + b; }
+  __device__ static SA s_rnd(SA a) { return F::rnd(a); }
+  __device__ static VA v_add(VA a, VA b) { return {a.lo + b.lo, a.hi + b.hi}; }
+  __device__ static VA v_rnd(VA a) { return {F::rnd4(a.lo), F::rnd4(a.hi)}; }
+};
+// folded hop by hop: every add rounds to the format (the one-round ring fold has
 // to reproduce the staged ring, which rounds once per hop)
-template <bool HW>
-struct BF16SumHopT : BF16SumT<HW> {
-  using B = BF16SumT<HW>;
+template <class F>
+struct H16SumHopT : H16SumT<F> {
+  using B = H16SumT<F>;
   using typename B::S;
   using typename B::SA;
   using typename B::VA;
-  __device__ static SA s_comb(SA a, S x) { return B::rnd(a + bf16_to_f32(x)); }
+  __device__ static SA s_comb(SA a, S x) { return F::rnd(a + F::widen(x)); }
   __device__ static VA v_comb(VA a, u32x4 x) {
     VA b = B::v_init(x);
     const f32x4 lo = a.lo + b.lo, hi = a.hi + b.hi;
-    return {B::rnd4(lo), B::rnd4(hi)};
+    return {F::rnd4(lo), F::rnd4(hi)};
   }
 };
 constexpr bool kHwBf16 = KHW_BF16_DEFAULT;
@@ -223,10 +260,12 @@ constexpr bool kHwBf16 = KHW_BF16_DEFAULT;
 // integer RNE their per-level rounds made them ALU-bound there (round 2: -2 to -25 %); with
 // v_cvt_pk_bf16_f32 rounding they gain +6.6 % and +3.6 % over the register kernel (cold,
 // profiles/r02/s4/kbench_nested_bf16_lds.log).  Runtime-coded bf16 shapes still lose there (2,3: -11 %,
-// 3,3: -4 %) and keep the register kernel.
+// 3,3: -4 %) and keep the register kernel.  fp16 rounds in hardware too and follows bf16's choices.
 constexpr bool kLdsDeepBf16 = KLDS_DEEP_BF16;
-using BF16Sum = BF16SumT<kHwBf16>;
-using BF16SumHop = BF16SumHopT<kHwBf16>;
+using BF16Sum = H16SumT<Bf16Fmt<kHwBf16>>;
+using BF16SumHop = H16SumHopT<Bf16Fmt<kHwBf16>>;
+using F16Sum = H16SumT<HalfFmt>;
+using F16SumHop = H16SumHopT<HalfFmt>;
 // modular integer sums on packed lanes (SWAR for 8/16-bit lanes)
 template <class S_, unsigned HI>
 struct SwarSum {
@@ -293,6 +332,62 @@ struct Band {
   __device__ static VA v_init(u32x4 x) { return x; }
   __device__ static VA v_comb(VA a, u32x4 x) { return a & x; }
   __device__ static u32x4 v_fin(VA a) { return a; }
+};
+
+// MAX / MIN (extensions): exact, associative and commutative, so one flat fold serves every schedule.
+// Integers compare by the dtype's signedness (v_pk_max_i16 and kin; 8-bit lanes are unpacked by the
+// compiler; 64-bit lanes compare and select).  Floats follow IEEE 754-2019 maximum / minimum
+// (v_maximum3_f32, v_pk_maximum3_f16, v_max_f64 plus a NaN select): -0 < +0, subnormals kept, any NaN
+// source makes the lane NaN, and a non-NaN result is one of the sources bit for bit.
+template <class T>
+constexpr bool kIsFloat = std::is_same_v<T, float> || std::is_same_v<T, double> || std::is_same_v<T, _Float16>;
+template <bool MAX, bool FLT, class V>  // V: a scalar or an ext-vector
+__device__ __forceinline__ V min_max(V a, V b) {
+  if constexpr (FLT) {
+    if constexpr (MAX) return __builtin_elementwise_maximum(a, b);
+    else return __builtin_elementwise_minimum(a, b);
+  } else {
+    if constexpr (MAX) return __builtin_elementwise_max(a, b);
+    else return __builtin_elementwise_min(a, b);
+  }
+}
+template <class T, bool MAX>
+struct MinMax {
+  using S = T;
+  using SA = T;
+  typedef T V __attribute__((ext_vector_type(16 / sizeof(T))));
+  using VA = V;
+  __device__ static SA s_init(S x) { return x; }
+  __device__ static SA s_comb(SA a, S x) { return min_max<MAX, kIsFloat<T>>(a, x); }
+  __device__ static S s_fin(SA a) { return a; }
+  __device__ static VA v_init(u32x4 x) { return __builtin_bit_cast(V, x); }
+  __device__ static VA v_comb(VA a, u32x4 x) { return min_max<MAX, kIsFloat<T>>(a, __builtin_bit_cast(V, x)); }
+  __device__ static u32x4 v_fin(VA a) { return __builtin_bit_cast(u32x4, a); }
+};
+// bf16 has no native maximum: widening is a 16-bit shift, the fp32 maximum of two widened values is one
+// of them (or a NaN, whose high half is a bf16 NaN), and its high half is the bf16 answer, exactly.
+template <bool MAX>
+struct BF16MinMax {
+  using S = unsigned short;
+  using SA = float;
+  struct VA {
+    f32x4 lo, hi;
+  };
+  using F = Bf16Fmt<false>;
+  __device__ static SA s_init(S x) { return F::widen(x); }
+  __device__ static SA s_comb(SA a, S x) { return min_max<MAX, true>(a, F::widen(x)); }
+  __device__ static S s_fin(SA a) { return (S)(__float_as_uint(a) >> 16); }
+  __device__ static VA v_init(u32x4 x) { return {F::unpack(x.x, x.y), F::unpack(x.z, x.w)}; }
+  __device__ static VA v_comb(VA a, u32x4 x) {
+    VA b = v_init(x);
+    return {min_max<MAX, true>(a.lo, b.lo), min_max<MAX, true>(a.hi, b.hi)};
+  }
+  __device__ static unsigned pack(float lo, float hi) {
+    return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
+  }
+  __device__ static u32x4 v_fin(VA a) {
+    return u32x4{pack(a.lo.x, a.lo.y), pack(a.lo.z, a.lo.w), pack(a.hi.x, a.hi.y), pack(a.hi.z, a.hi.w)};
+  }
 };
 
 template <int K>

@@ -13,7 +13,7 @@ namespace ftar {
 size_t dtype_size(ftar_dtype_t dt) {
   switch (dt) {
     case FTAR_UINT8: case FTAR_INT8: case FTAR_BOOL: return 1;
-    case FTAR_UINT16: case FTAR_INT16: case FTAR_BFLOAT16: return 2;
+    case FTAR_UINT16: case FTAR_INT16: case FTAR_BFLOAT16: case FTAR_FLOAT16: return 2;
     case FTAR_INT32: case FTAR_FLOAT32: return 4;
     case FTAR_INT64: case FTAR_FLOAT64: return 8;
   }
@@ -22,10 +22,13 @@ size_t dtype_size(ftar_dtype_t dt) {
 
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op) {
   if (dtype_size(dt) == 0) return false;
-  if (op == FTAR_SUM) return true;
-  if (op == FTAR_BAND)  // mpi_mod.hpp:1389-1396: integer types only
-    return dt == FTAR_UINT8 || dt == FTAR_INT8 || dt == FTAR_UINT16 || dt == FTAR_INT16 || dt == FTAR_INT32 ||
-           dt == FTAR_INT64;
+  switch (op) {
+    case FTAR_SUM: return true;
+    case FTAR_BAND:  // mpi_mod.hpp:1389-1396: integer types only
+      return dt == FTAR_UINT8 || dt == FTAR_INT8 || dt == FTAR_UINT16 || dt == FTAR_INT16 || dt == FTAR_INT32 ||
+             dt == FTAR_INT64;
+    case FTAR_MAX: case FTAR_MIN: return dt != FTAR_BOOL;  // MPI defines no MAX / MIN on logical types either
+  }
   return false;
 }
 
@@ -111,6 +114,25 @@ template <class Tr, int HOT>
 hipError_t tr(bool lds, const void* const* srcs, int k, void* dst, size_t count, hipStream_t s) {
   return lds ? launch_tr<Tr, HOT>(srcs, k, dst, count, s) : launch_tr<Tr, 0>(srcs, k, dst, count, s);
 }
+// MAX / MIN of one dtype; HOT as the SUM of the same element width
+template <bool MAX>
+hipError_t tr_min_max(ftar_dtype_t dt, bool lds, const void* const* srcs, int k, void* dst, size_t count,
+                      hipStream_t s) {
+  switch (dt) {
+    case FTAR_UINT8: return tr<MinMax<unsigned char, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_INT8: return tr<MinMax<signed char, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_UINT16: return tr<MinMax<unsigned short, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_INT16: return tr<MinMax<short, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_INT32: return tr<MinMax<int, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_INT64: return tr<MinMax<long long, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_FLOAT32: return tr<MinMax<float, MAX>, 16>(lds, srcs, k, dst, count, s);
+    case FTAR_FLOAT64: return tr<MinMax<double, MAX>, 8>(lds, srcs, k, dst, count, s);
+    case FTAR_BFLOAT16: return tr<BF16MinMax<MAX>, 16>(lds, srcs, k, dst, count, s);
+    case FTAR_FLOAT16: return tr<MinMax<_Float16, MAX>, 16>(lds, srcs, k, dst, count, s);
+    case FTAR_BOOL: break;
+  }
+  return hipErrorInvalidValue;
+}
 }  // namespace
 
 // The LDS-staged kernel with K = 1 on one-wave workgroups of one tile (U = 1, W = 1; byte traits, so any
@@ -143,23 +165,30 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
   if (k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)
     return launch_copy(srcs[0], dst, count * dtype_size(dt), s);
   hipError_t e = hipErrorInvalidValue;
-  if (nlevels > 1 && op == FTAR_SUM && (dt == FTAR_FLOAT32 || dt == FTAR_FLOAT64 || dt == FTAR_BFLOAT16)) {
+  if (nlevels > 1 && op == FTAR_SUM &&
+      (dt == FTAR_FLOAT32 || dt == FTAR_FLOAT64 || dt == FTAR_BFLOAT16 || dt == FTAR_FLOAT16)) {
     TreeCode tc;
     if (!shape || !make_tree_code(shape, nlevels, k, &tc)) return FTAR_ERR_INVALID_ARG;
     switch (dt) {
       case FTAR_FLOAT32: e = launch_tree<F32Sum>(srcs, k, tc, shape, nlevels, dst, count, s, lds); break;
       case FTAR_FLOAT64: e = launch_tree<F64Sum>(srcs, k, tc, shape, nlevels, dst, count, s, false); break;
+      case FTAR_FLOAT16: e = launch_tree<F16Sum>(srcs, k, tc, shape, nlevels, dst, count, s, lds); break;
       default: e = launch_tree<BF16Sum>(srcs, k, tc, shape, nlevels, dst, count, s, lds); break;
     }
     FTAR_CHECK_HIP(e);
     return FTAR_SUCCESS;
   }
-  if (op == FTAR_SUM) {
+  switch (op) {
+  case FTAR_SUM:
     switch (dt) {
       case FTAR_FLOAT32: e = tr<F32Sum, 16>(lds, srcs, k, dst, count, s); break;
       case FTAR_BFLOAT16:
         e = round_each && k > 2 ? tr<BF16SumHop, 16>(lds, srcs, k, dst, count, s)
                                 : tr<BF16Sum, 16>(lds, srcs, k, dst, count, s);
+        break;
+      case FTAR_FLOAT16:
+        e = round_each && k > 2 ? tr<F16SumHop, 16>(lds, srcs, k, dst, count, s)
+                                : tr<F16Sum, 16>(lds, srcs, k, dst, count, s);
         break;
       case FTAR_FLOAT64: e = tr<F64Sum, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_UINT8: case FTAR_INT8: e = tr<U8Sum, 8>(lds, srcs, k, dst, count, s); break;
@@ -168,7 +197,8 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
       case FTAR_INT64: e = tr<U64Sum, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_BOOL: e = tr<BoolSum, 8>(lds, srcs, k, dst, count, s); break;
     }
-  } else {
+    break;
+  case FTAR_BAND:
     switch (dt) {
       case FTAR_UINT8: case FTAR_INT8: e = tr<Band<unsigned char>, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_UINT16: case FTAR_INT16: e = tr<Band<unsigned short>, 8>(lds, srcs, k, dst, count, s); break;
@@ -176,6 +206,9 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
       case FTAR_INT64: e = tr<Band<unsigned long long>, 8>(lds, srcs, k, dst, count, s); break;
       default: return FTAR_ERR_UNSUPPORTED;
     }
+    break;
+  case FTAR_MAX: e = tr_min_max<true>(dt, lds, srcs, k, dst, count, s); break;
+  case FTAR_MIN: e = tr_min_max<false>(dt, lds, srcs, k, dst, count, s); break;
   }
   FTAR_CHECK_HIP(e);
   return FTAR_SUCCESS;

@@ -405,10 +405,17 @@ class RcclTransport final : public Transport {
       case FTAR_FLOAT32: t = ncclFloat32; break;
       case FTAR_FLOAT64: t = ncclFloat64; break;
       case FTAR_BFLOAT16: t = ncclBfloat16; break;
+      case FTAR_FLOAT16: t = ncclFloat16; break;
       default: return FTAR_ERR_UNSUPPORTED;
     }
-    if (op != FTAR_SUM) return FTAR_ERR_UNSUPPORTED;
-    FTAR_CHECK_NCCL(ncclAllReduce(send ? send : recv, recv, count, t, ncclSum, comm_, s));
+    ncclRedOp_t o;
+    switch (op) {  // RCCL's own arithmetic: its NaN and signed-zero rules for max / min are not ftar's contract
+      case FTAR_SUM: o = ncclSum; break;
+      case FTAR_MAX: o = ncclMax; break;
+      case FTAR_MIN: o = ncclMin; break;
+      default: return FTAR_ERR_UNSUPPORTED;
+    }
+    FTAR_CHECK_NCCL(ncclAllReduce(send ? send : recv, recv, count, t, o, comm_, s));
     return FTAR_SUCCESS;
   }
 

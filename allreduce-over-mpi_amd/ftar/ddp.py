@@ -12,6 +12,12 @@ stream.
     model = DistributedDataParallel(model, device_ids=[local_rank])
     model.register_comm_hook(ftar.ddp.HookState(comm), ftar.ddp.allreduce_hook)
 
+The bucket's dtype is the tensor's own: fp32, bf16 and fp16 gradient buckets all work (mixed-precision
+training, or DDP's fp16 / bf16 compression wrappers around this hook).  The 16-bit sums accumulate in fp32 and
+round once per reduce call (include/ftar.h); an fp16 sum that overflows becomes inf, which a loss scaler sees.
+The collectives such training needs next to the sum -- overflow flags, inf-norms for clipping, loss-scale
+agreement -- are `comm.allreduce_tensor(t, op="max")` / `op="min"`.
+
 The reference reduces MPI buffers (MPI_Allreduce_FT, mpi_mod.hpp:1723-1778); a DDP bucket is the same call on
 a device tensor, in place (`sendbuf = MPI_IN_PLACE`).
 """

@@ -52,13 +52,38 @@ typedef enum {
   FTAR_FLOAT32 = 6, /* MPI_FLOAT */
   FTAR_FLOAT64 = 7, /* MPI_DOUBLE */
   FTAR_BOOL = 8,    /* MPI_C_BOOL: sum of bools == logical OR */
-  FTAR_BFLOAT16 = 9 /* extension: fp32 accumulate, one RNE rounding per reduce */
+  FTAR_BFLOAT16 = 9, /* extension: fp32 accumulate, one RNE rounding per reduce */
+  FTAR_FLOAT16 = 10  /* extension: IEEE binary16, bf16's rules (see below) */
 } ftar_dtype_t;
 
 typedef enum {
   FTAR_SUM = 0,  /* MPI_SUM */
-  FTAR_BAND = 1  /* MPI_BAND (integer types only, as in the reference) */
+  FTAR_BAND = 1, /* MPI_BAND (integer types only, as in the reference) */
+  FTAR_MAX = 2,  /* extension: every dtype but FTAR_BOOL (see below) */
+  FTAR_MIN = 3   /* extension: every dtype but FTAR_BOOL */
 } ftar_op_t;
+
+/* Which (dtype, op) pairs run; the rest return FTAR_ERR_UNSUPPORTED before any device work.
+ *
+ *                  SUM   BAND   MAX   MIN
+ *   u8 i8 u16 i16   x     x      x     x
+ *   i32 i64         x     x      x     x
+ *   f32 f64         x     -      x     x
+ *   bf16 f16        x     -      x     x
+ *   bool            x(OR) -      -     -      (MPI defines no MAX/MIN on logical types either)
+ *
+ * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
+ * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
+ * ring, once per node of a multi-stage tree.  For binary16 that rounding overflows to +-inf, keeps results
+ * in the subnormal range (gradual underflow), and reads subnormal inputs exactly.  A lane is NaN exactly
+ * where that fold has a NaN; which NaN is not specified.
+ *
+ * MAX / MIN: integers compare by the dtype's signedness (the first place u8/i8 and u16/i16 differ; SUM and
+ * BAND treat them alike).  Floats follow IEEE 754-2019 maximum / minimum: -0 < +0, subnormals are not
+ * flushed, a non-NaN result is bit for bit one of the sources, and any NaN source makes the lane NaN
+ * (payload unspecified).  Both are exact, associative and commutative, so every topology, form, piece size
+ * and buffer kind gives the same bits, and a nested shape (ftar_reduce_nested) has no effect on them.
+ * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
   FTAR_SUCCESS = 0,
@@ -93,7 +118,8 @@ const char* ftar_last_error(void);
 size_t ftar_dtype_size(ftar_dtype_t dt);
 
 /* ---- L3: k-way element-wise reduce on one device -------------------------
- * dst[i] = srcs[0][i] (+|&) srcs[1][i] (+|&) ... left to right, i < count.
+ * dst[i] = srcs[0][i] OP srcs[1][i] OP ... left to right, i < count; OP is
+ * + (SUM), & (BAND), max or min (the support matrix is at ftar_op_t above).
  * srcs: HOST array of k device pointers; dst may alias srcs[0] (in place).
  * k == 1 copies (vector_add/reduce_sum.h:36-47).  stream: hipStream_t. */
 ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
@@ -102,10 +128,10 @@ ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t coun
  * the k sources are the leaves, in depth-first order, of a mixed-radix tree
  * with bottom-up widths shape[0..nlevels) (product == k, nlevels <= 4).  Level
  * 0 folds shape[0] consecutive leaves, level 1 folds shape[1] consecutive
- * level-0 results, ... each node left to right; bf16 inner nodes are rounded
- * to bf16 (what a staged tree stores between its stages).  Integer sums and
- * AND are associative: the result equals ftar_reduce's.  nlevels <= 1 is
- * ftar_reduce. */
+ * level-0 results, ... each node left to right; bf16 and fp16 inner nodes
+ * are rounded to their format (what a staged tree stores between its stages).
+ * Integer sums, AND, MAX and MIN are associative: the result equals
+ * ftar_reduce's (the flat kernel runs).  nlevels <= 1 is ftar_reduce. */
 ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  ftar_op_t op, const int* shape, int nlevels, void* stream);
 
@@ -306,7 +332,7 @@ ftar_status_t ftar_comm_get_allgather(ftar_comm_t comm, ftar_allgather_t* mode);
  *   FTAR_RS_STAGES  the reference's P-1 neighbour steps (one xGMI link per rank)
  *   FTAR_RS_DIRECT  rank b-1 gathers every rank's block b in ONE round over all
  *                   links and folds them in that order with one k=P reduce
- *                   (bf16: rounded after every add, i.e. once per hop, as staged)
+ *                   (bf16, fp16: rounded after every add, i.e. once per hop, as staged)
  * Identical results.  Multi-stage trees without lonely ranks (at most 4
  * stages) likewise: FTAR_RS_DIRECT gathers the P copies of block r on rank r
  * in one round and folds them as the tree would (ftar_reduce_nested), bit for
@@ -408,7 +434,10 @@ ftar_status_t ftar_comm_get_host_chunk_bytes(ftar_comm_t comm, size_t* bytes);
 /* ---- diagnostics ---------------------------------------------------------------
  * RCCL's own ncclAllReduce on the communicator's RCCL comm (ring/tree of the
  * vendor library, reduction inside RCCL): the yardstick bench.py reports next
- * to ftar at N > 1.  FTAR_ERR_UNSUPPORTED on local (in-process) groups. */
+ * to ftar at N > 1.  FTAR_ERR_UNSUPPORTED on local (in-process) groups, for
+ * the types RCCL lacks (u16, i16, bool) and for BAND.  SUM, MAX and MIN map to
+ * ncclSum / ncclMax / ncclMin, fp16 to ncclFloat16: the arithmetic is RCCL's,
+ * so its NaN and signed-zero rules for max / min may differ from ftar's. */
 ftar_status_t ftar_rccl_allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dtype, ftar_op_t op,
                                   ftar_comm_t comm, void* stream);
 /* xGMI calibration (collective; every rank calls it): GB/s seen by this rank

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """ftar_reduce (the production dispatch) by dtype and k on cold data: launches rotate over 4 disjoint
 (k sources + destination) sets of 256 MiB buffers; GB/s of (k+1) x 256 MiB algorithmic bytes, median of
-interleaved rounds.  python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f64,i32,i16,u8,bool]"""
+interleaved rounds, with the slowest and fastest round next to it (the run's own spread: the margin when
+one (dtype, op) is judged against another of the same width).  --op takes a list; pairs the library
+refuses (band on floats, max on bool) are skipped.
+python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f16,f64,i32,i16,u8,bool] [--op sum,max,min]"""
 import argparse
 import json
 import os
@@ -16,7 +19,7 @@ import ftar  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--ks", default="2,8")
 ap.add_argument("--dtypes", default="f32,bf16,f64,i64,i32,i16,u8,bool")
-ap.add_argument("--op", default="sum")
+ap.add_argument("--op", default="sum", help="one op or a comma list: sum,band,max,min")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=8)
 a = ap.parse_args()
@@ -26,23 +29,36 @@ S = 4
 bufs = [[torch.randint(0, 256, (NB,), dtype=torch.uint8, device="cuda") for _ in range(max(ks) + 1)] for _ in range(S)]
 stream = torch.cuda.current_stream()
 res = {}
+ops = a.op.split(",")
+refused = set()
 for _ in range(a.rounds):
-    for d in a.dtypes.split(","):
+    for d, op in ((d, op) for d in a.dtypes.split(",") for op in ops):
         n = NB // ftar.dtype_size(d)
         for k in ks:
             def launch(i):
                 s = bufs[i % S]
-                ftar.reduce(s[:k], s[max(ks)], n, d, a.op, stream=stream)
-            for i in range(S):
-                launch(i)
+                ftar.reduce(s[:k], s[max(ks)], n, d, op, stream=stream)
+            if (d, op) in refused:
+                continue
+            try:
+                for i in range(S):
+                    launch(i)
+            except ftar.FtarError as e:
+                if e.status != 2:   # "unsupported": not a pair of this library
+                    raise
+                refused.add((d, op))
+                continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
             for i in range(a.reps):
                 launch(i)
             e1.record(stream)
             torch.cuda.synchronize()
-            res.setdefault((d, k), []).append(e0.elapsed_time(e1) / a.reps)
-for (d, k), ts in res.items():
+            res.setdefault((d, op, k), []).append(e0.elapsed_time(e1) / a.reps)
+for (d, op, k), ts in res.items():
     med = statistics.median(ts)
-    print(json.dumps({"dtype": d, "op": a.op, "k": k, "ms_med": round(med, 4),
-                      "GBps_med": round((k + 1) * NB / med / 1e6, 1)}), flush=True)
+
+    def rate(ms):
+        return round((k + 1) * NB / ms / 1e6, 1)
+    print(json.dumps({"dtype": d, "op": op, "k": k, "ms_med": round(med, 4), "GBps_med": rate(med),
+                      "GBps_slowest": rate(max(ts)), "GBps_fastest": rate(min(ts))}), flush=True)

@@ -89,4 +89,5 @@ for (d, sets, k, v), ts in sorted(res.items(), key=lambda kv: str(kv[0])):
     byts = (kk + 1) * n * 4
     print(json.dumps({"dtype": d, "sets": sets, "k": k, "variant": v, "inplace": a.inplace, "bytes_per_buffer": n * 4,
                       "ms_med": round(med, 4),
-                      "GBps_med": round(byts / med / 1e6, 1), "GBps_max": round(byts / min(ts) / 1e6, 1)}), flush=True)
+                      "GBps_med": round(byts / med / 1e6, 1), "GBps_max": round(byts / min(ts) / 1e6, 1),
+                      "GBps_min": round(byts / max(ts) / 1e6, 1)}), flush=True)
