@@ -218,6 +218,25 @@ ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size
                              nlevels);
 }
 
+ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
+                                 double scale, const int* shape, int nlevels, void* stream) {
+  if (!ftar::dtype_scalable(dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!std::isfinite(scale)) return FTAR_ERR_INVALID_ARG;
+  if (nlevels < 0 || nlevels > ftar::kMaxFoldLevels || (nlevels > 0 && !shape)) return FTAR_ERR_INVALID_ARG;
+  if (nlevels > 1) {
+    long long prod = 1;
+    for (int l = 0; l < nlevels; ++l) {
+      if (shape[l] < 1) return FTAR_ERR_INVALID_ARG;
+      prod *= shape[l];
+    }
+    if (prod != k) return FTAR_ERR_INVALID_ARG;
+  }
+  // the kernels multiply by the scale as a float (f64: as it is); the cast happens at the launch
+  const double r = dtype == FTAR_FLOAT64 ? scale : (double)(float)scale;
+  return ftar::launch_reduce(srcs, k, dst, count, dtype, FTAR_SUM, static_cast<hipStream_t>(stream), false, shape,
+                             nlevels, true, &r);
+}
+
 // get_stages (mpi_mod.hpp:1419-1486), minus its two bugs: an unset FT_TOPO
 // is reported (the reference exit(1)s for every P > 1) and a trailing comma
 // does not repeat the last width (the reference's `while(!ss.eof())` does).

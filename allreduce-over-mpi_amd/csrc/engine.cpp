@@ -672,6 +672,7 @@ ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count,
   const Plan* planp = nullptr;
   FTAR_RETURN_IF(resolve_plan(c, topology, count, form, &planp));
   const Plan& plan = *planp;
+  const FoldOp fo = fold_op(op, dt, c->nranks);  // AVG: SUM, scaled by 1 / P on the plan's root items
   // what runs (ftar_comm_last_exec): the model's or the settings' form, unless the plan or the buffers send
   // the call down another path below (host buffers on a p2p transport, a plan no peer kernel runs, the
   // collective all-gather a ring or host buffers replace)
@@ -876,8 +877,8 @@ ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count,
         srcs.clear();
         for (const Operand& o : r.srcs) srcs.push_back(sbuf(o.buf, o.off + lo, s));
         FTAR_RETURN_IF(launch_reduce(srcs.data(), (int)srcs.size(), bufs[BUF_DST] + (r.off + lo) * esz,
-                                     std::min(chunk, r.len - lo), dt, op, c->red_s, r.round_each, r.shape.data(),
-                                     (int)r.shape.size()));
+                                     std::min(chunk, r.len - lo), dt, fo.op, c->red_s, r.round_each, r.shape.data(),
+                                     (int)r.shape.size(), true, fo.scale(r.root)));
       }
       FTAR_CHECK_HIP(hipEventRecord(ev_r(s, k), c->red_s));
     }

@@ -139,8 +139,9 @@ ftar_status_t peer_fold(const ReduceItem& r, const Plan& plan, ftar_dtype_t dt, 
     }
   }
   if (lo >= r.len) return FTAR_SUCCESS;
-  return launch_reduce(srcs.data(), (int)srcs.size(), dst, std::min(len, r.len - lo), dt, op, s, r.round_each,
-                       r.shape.data(), (int)r.shape.size(), lds);
+  const FoldOp fo = fold_op(op, dt, plan.nranks);  // AVG: SUM, scaled on the root item (every piece of it)
+  return launch_reduce(srcs.data(), (int)srcs.size(), dst, std::min(len, r.len - lo), dt, fo.op, s, r.round_each,
+                       r.shape.data(), (int)r.shape.size(), lds, fo.scale(r.root));
 }
 
 namespace {

@@ -29,7 +29,9 @@
 //       bool sum = OR of non-zero;
 //   * extensions (no reference): bf16 and fp16 sums = fp32 accumulate + one RNE per
 //     reduce; MAX / MIN = signed or unsigned integer compare, IEEE 754-2019
-//     maximum / minimum on floats (exact: every fold order gives the same bits).
+//     maximum / minimum on floats (exact: every fold order gives the same bits); the scaled float sums
+//     (AVG's root fold, ftar_reduce_scaled): the accumulator times r before the fold's one rounding, on
+//     *_scaled_kernel twins of the fold kernels (ScaledFin below).
 #pragma once
 // Internal: the reduce kernels, their traits and launchers, included by reduce_kernels.hip (the
 // production dispatch, libftar.so) and bench_kernels.hip (the A/B harness, libftar_bench.so);
@@ -129,6 +131,15 @@ __device__ __forceinline__ unsigned bf16_round_bits(float f) {  // result in the
 }
 __device__ __forceinline__ unsigned short f32_to_bf16(float f) { return (unsigned short)(bf16_round_bits(f) >> 16); }
 
+// a * r rounded in a's own precision, whatever follows: with contraction allowed (hipcc's default) the
+// compiler fuses an fp32 multiply into the conversion after it (v_fma_mixlo_f16: the exact product rounded
+// once, to fp16), which is not the scaled finish's fp32 product followed by the fold's RNE
+template <class A, class R>
+__device__ __forceinline__ A mul_rn(A a, R r) {
+#pragma clang fp contract(off)
+  return a * r;
+}
+
 // ---------------------------------------------------------------------------
 // element traits: scalar (S*) and 16-byte vector (V*) forms of one (dtype, op)
 // ---------------------------------------------------------------------------
@@ -146,6 +157,9 @@ struct F32Sum {
   __device__ static SA s_rnd(SA a) { return a; }
   __device__ static VA v_add(VA a, VA b) { return a + b; }
   __device__ static VA v_rnd(VA a) { return a; }
+  using SC = float;  // scaled finish (ScaledFin): one multiply in the accumulator's precision
+  __device__ static SA s_scale(SA a, SC r) { return mul_rn(a, r); }
+  __device__ static VA v_scale(VA a, SC r) { return mul_rn(a, r); }
 };
 struct F64Sum {
   using S = double;
@@ -161,6 +175,9 @@ struct F64Sum {
   __device__ static SA s_rnd(SA a) { return a; }
   __device__ static VA v_add(VA a, VA b) { return a + b; }
   __device__ static VA v_rnd(VA a) { return a; }
+  using SC = double;
+  __device__ static SA s_scale(SA a, SC r) { return mul_rn(a, r); }
+  __device__ static VA v_scale(VA a, SC r) { return mul_rn(a, r); }
 };
 // bf16 rounding of two floats at once.  HW: gfx950's v_cvt_pk_bf16_f32 (RNE); every one of the 2^32
 // float bit patterns converts to the same bf16 bits as bf16_round_bits, NaNs included
@@ -239,6 +256,13 @@ struct H16SumT {
   __device__ static SA s_rnd(SA a) { return F::rnd(a); }
   __device__ static VA v_add(VA a, VA b) { return {a.lo + b.lo, a.hi + b.hi}; }
   __device__ static VA v_rnd(VA a) { return {F::rnd4(a.lo), F::rnd4(a.hi)}; }
+  using SC = float;  // the fp32 accumulator times r (v_pk_mul_f32), then the fold's one RNE
+  __device__ static SA s_scale(SA a, SC r) {  // head / tail elements: the product lands in a register first,
+    float p = mul_rn(a, r);                   // so the narrowing after it is a conversion of its own (never one
+    asm volatile("" : "+v"(p));               // v_fma_mixlo_f16 of the unrounded product)
+    return p;
+  }
+  __device__ static VA v_scale(VA a, SC r) { return {mul_rn(a.lo, r), mul_rn(a.hi, r)}; }
 };
 // folded hop by hop: every add rounds to the format (the one-round ring fold has
 // to reproduce the staged ring, which rounds once per hop)
@@ -255,6 +279,21 @@ struct H16SumHopT : H16SumT<F> {
     return {F::rnd4(lo), F::rnd4(hi)};
   }
 };
+// the hop fold under a scaled finish: the staged ring's last hop is a plain k = 2 fold that rounds
+// (a + b) * r once, so here the accumulator is rounded BEFORE each add (a no-op on the first operand,
+// already in the format) and the last sum reaches the finisher unrounded
+template <class F>
+struct H16SumHopPreT : H16SumT<F> {
+  using B = H16SumT<F>;
+  using typename B::S;
+  using typename B::SA;
+  using typename B::VA;
+  __device__ static SA s_comb(SA a, S x) { return F::rnd(a) + F::widen(x); }
+  __device__ static VA v_comb(VA a, u32x4 x) {
+    VA b = B::v_init(x);
+    return {F::rnd4(a.lo) + b.lo, F::rnd4(a.hi) + b.hi};
+  }
+};
 constexpr bool kHwBf16 = KHW_BF16_DEFAULT;
 // bf16 nested folds of three and four levels (2,2,2), (2,2,2,2) on the LDS-staged kernel: with the
 // integer RNE their per-level rounds made them ALU-bound there (round 2: -2 to -25 %); with
@@ -266,6 +305,8 @@ using BF16Sum = H16SumT<Bf16Fmt<kHwBf16>>;
 using BF16SumHop = H16SumHopT<Bf16Fmt<kHwBf16>>;
 using F16Sum = H16SumT<HalfFmt>;
 using F16SumHop = H16SumHopT<HalfFmt>;
+using BF16SumHopPre = H16SumHopPreT<Bf16Fmt<kHwBf16>>;
+using F16SumHopPre = H16SumHopPreT<HalfFmt>;
 // modular integer sums on packed lanes (SWAR for 8/16-bit lanes)
 template <class S_, unsigned HI>
 struct SwarSum {
@@ -390,6 +431,20 @@ struct BF16MinMax {
   }
 };
 
+// The scaled finish (AVG's root fold, ftar_reduce_scaled; the float sums): out = round_to_dtype(A * r), one
+// multiply in the accumulator's precision (fp32 for bf16 / fp16; subnormal products kept), then the
+// fold's single rounding.  The scale is a kernarg of the *_scaled_kernel twins below: instantiations of
+// their own, next to the kernels every other op launches, whose code is not shared with them and so
+// compiles to what it was.
+template <class Tr>
+struct ScaledFin {
+  typename Tr::SC r;
+  __device__ typename Tr::S s(typename Tr::SA a) const { return Tr::s_fin(Tr::s_scale(a, r)); }
+  __device__ u32x4 v(typename Tr::VA a) const { return Tr::v_fin(Tr::v_scale(a, r)); }
+};
+// Host side: a launcher's template argument SC = true, with the scale r (cast to Tr::SC at the launch), launches
+// the scaled twin; each twin is a *_body (the parent kernel's loop with `fin` as its finish) and its __global__.
+
 template <int K>
 struct Srcs {
   const void* p[K];
@@ -460,6 +515,76 @@ __global__ void __launch_bounds__(BS)
       a = Tr::v_comb(a, ld16<NTL>(reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head) + v));
     st16<NTS>(d + v, Tr::v_fin(a));
   }
+}
+
+// The scaled twin: reduce_vec_kernel with a ScaledFin finish (its own instantiation; the kernel above is
+// what every other op launches, untouched).
+template <class Tr, int K, int U, bool NTL, bool NTS, int BS>
+__device__ __forceinline__ void reduce_vec_body(const Srcs<(K > 0 ? K : FTAR_MAX_K)>& src, int kr, void* dst,
+                                                size_t nvec, int head, int tail, ScaledFin<Tr> fin) {
+  using S = typename Tr::S;
+  constexpr int KK = K > 0 ? K : FTAR_MAX_K;
+  const int k = K > 0 ? K : kr;
+  constexpr int VE = 16 / sizeof(S);
+  constexpr int kThreads = BS;
+  const size_t tile_stride = (size_t)gridDim.x * (U * kThreads);
+  size_t v0 = (size_t)blockIdx.x * (U * kThreads) + threadIdx.x;
+
+  if (blockIdx.x == 0 && threadIdx.x < (unsigned)(head + tail)) {  // unaligned head / short tail
+    const size_t e = threadIdx.x < (unsigned)head ? threadIdx.x : (size_t)head + nvec * VE + (threadIdx.x - head);
+    typename Tr::SA a = Tr::s_init(static_cast<const S*>(src.p[0])[e]);
+    for (int j = 1; j < k; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
+    static_cast<S*>(dst)[e] = fin.s(a);
+  }
+
+  const u32x4* s0 = reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[0]) + head);
+  u32x4* d = reinterpret_cast<u32x4*>(static_cast<S*>(dst) + head);
+  for (; v0 + (U - 1) * kThreads < nvec; v0 += tile_stride) {  // full tiles: no per-vector guards
+    typename Tr::VA acc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] = Tr::v_init(ld16<NTL>(s0 + v0 + u * kThreads));
+    if constexpr (K > 0) {
+      u32x4 x[KK > 1 ? KK - 1 : 1][U];
+#pragma unroll
+      for (int j = 1; j < KK; ++j) {
+        const u32x4* sj = reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head);
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[j - 1][u] = ld16<NTL>(sj + v0 + u * kThreads);
+      }
+#pragma unroll
+      for (int j = 1; j < KK; ++j)
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[u] = Tr::v_comb(acc[u], x[j - 1][u]);
+    } else {
+      for (int j = 1; j < k; ++j) {
+        const u32x4* sj = reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head);
+        u32x4 x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[u] = ld16<NTL>(sj + v0 + u * kThreads);
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[u] = Tr::v_comb(acc[u], x[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) st16<NTS>(d + v0 + u * kThreads, fin.v(acc[u]));
+  }
+  // the one partial tile (if any): guarded
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const size_t v = v0 + u * kThreads;
+    if (v >= nvec) break;
+    typename Tr::VA a = Tr::v_init(ld16<NTL>(s0 + v));
+    for (int j = 1; j < k; ++j)
+      a = Tr::v_comb(a, ld16<NTL>(reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head) + v));
+    st16<NTS>(d + v, fin.v(a));
+  }
+}
+
+template <class Tr, int K, int U, bool NTL, bool NTS, int BS = kThreads>
+__global__ void __launch_bounds__(BS)
+    reduce_vec_scaled_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, void* dst, size_t nvec, int head,
+                             int tail, typename Tr::SC scale) {
+  reduce_vec_body<Tr, K, U, NTL, NTS, BS>(src, kr, dst, nvec, head, tail, ScaledFin<Tr>{scale});
 }
 
 // LDS-staged reduce: the production kernel for k = 2..16 (launch_k; A/B
@@ -547,8 +672,33 @@ __global__ void __launch_bounds__(W * 64)
       });
 }
 
-template <class Tr, int K, int U, int W = 4, int AUX = 2, bool PROG = true>
-hipError_t launch_lds(const void* const* srcs, void* dst, size_t nvec, hipStream_t s, int head = 0, int tail = 0) {
+template <class Tr, int K, int U, int W, int AUX, bool PROG>
+__device__ __forceinline__ void reduce_lds_body(const Srcs<K>& src, void* dst, size_t nvec, int head, int tail,
+                                                ScaledFin<Tr> fin) {
+  using S = typename Tr::S;
+  lds_staged<Tr, K, U, W, AUX, PROG>(
+      src, dst, nvec, head, tail,
+      [&](auto get) {
+        typename Tr::VA a = Tr::v_init(get(0));
+#pragma unroll
+        for (int j = 1; j < K; ++j) a = Tr::v_comb(a, get(j));
+        return fin.v(a);
+      },
+      [&](size_t e) {
+        typename Tr::SA a = Tr::s_init(static_cast<const S*>(src.p[0])[e]);
+        for (int j = 1; j < K; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
+        return fin.s(a);
+      });
+}
+template <class Tr, int K, int U, int W, int AUX, bool PROG>
+__global__ void __launch_bounds__(W * 64)
+    reduce_lds_scaled_kernel(Srcs<K> src, void* dst, size_t nvec, int head, int tail, typename Tr::SC scale) {
+  reduce_lds_body<Tr, K, U, W, AUX, PROG>(src, dst, nvec, head, tail, ScaledFin<Tr>{scale});
+}
+
+template <class Tr, int K, int U, int W = 4, int AUX = 2, bool PROG = true, bool SC = false>
+hipError_t launch_lds(const void* const* srcs, void* dst, size_t nvec, hipStream_t s, int head = 0, int tail = 0,
+                      double r = 1.0) {
   if constexpr (W * U * K > 160) {
     return hipErrorInvalidValue;
   } else {
@@ -556,8 +706,12 @@ hipError_t launch_lds(const void* const* srcs, void* dst, size_t nvec, hipStream
     for (int j = 0; j < K; ++j) a.p[j] = srcs[j];
     const size_t per_block = (size_t)W * U * 64;
     const size_t blocks = (nvec + per_block - 1) / per_block;
-    FTAR_LAUNCH((reduce_lds_kernel<Tr, K, U, W, AUX, PROG>), dim3((unsigned)(blocks ? blocks : 1)),
-                       dim3(W * 64), 0, s, a, dst, nvec, head, tail);
+    const dim3 grid((unsigned)(blocks ? blocks : 1));
+    if constexpr (SC)
+      FTAR_LAUNCH((reduce_lds_scaled_kernel<Tr, K, U, W, AUX, PROG>), grid, dim3(W * 64), 0, s, a, dst, nvec, head,
+                  tail, (typename Tr::SC)r);
+    else
+      FTAR_LAUNCH((reduce_lds_kernel<Tr, K, U, W, AUX, PROG>), grid, dim3(W * 64), 0, s, a, dst, nvec, head, tail);
     return hipGetLastError();
   }
 }
@@ -573,6 +727,22 @@ __global__ void __launch_bounds__(kThreads)
     for (int j = 1; j < k; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
     static_cast<S*>(dst)[e] = Tr::s_fin(a);
   }
+}
+template <class Tr>
+__device__ __forceinline__ void reduce_elem_body(const Srcs<FTAR_MAX_K>& src, int k, void* dst, size_t n,
+                                                 ScaledFin<Tr> fin) {
+  using S = typename Tr::S;
+  const size_t stride = (size_t)gridDim.x * kThreads;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride) {
+    typename Tr::SA a = Tr::s_init(static_cast<const S*>(src.p[0])[e]);
+    for (int j = 1; j < k; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
+    static_cast<S*>(dst)[e] = fin.s(a);
+  }
+}
+template <class Tr>
+__global__ void __launch_bounds__(kThreads)
+    reduce_elem_scaled_kernel(Srcs<FTAR_MAX_K> src, int k, void* dst, size_t n, typename Tr::SC scale) {
+  reduce_elem_body<Tr>(src, k, dst, n, ScaledFin<Tr>{scale});
 }
 
 // ---------------------------------------------------------------------------
@@ -755,6 +925,140 @@ __global__ void __launch_bounds__(W * 64)
       [&](size_t e) { return tree_elem<Tr>(src.p, K, tc, e); });
 }
 
+// The scaled nested fold: as tree_push, but the last leaf (`last`) leaves the root in v as its
+// level's accumulator holds it, unrounded, for the finisher to scale and round once; inner nodes are
+// rounded as ever.  The last leaf completes every level (done = L), so the root is the node that closes
+// at level done - 1.
+template <class O, int U>
+__device__ __forceinline__ void tree_push_root(typename O::A (&acc)[kTreeLevels][U], typename O::A (&v)[U],
+                                               unsigned code, bool last) {
+  const unsigned done = code & 7u;
+#pragma unroll
+  for (int l = 0; l < kTreeLevels; ++l) {
+    const bool fresh = (code >> (3 + l)) & 1u;
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[l][u] = fresh ? v[u] : O::add(acc[l][u], v[u]);
+    if (done <= (unsigned)l) break;
+    const bool root = last && done == (unsigned)l + 1;
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = root ? acc[l][u] : O::rnd(acc[l][u]);
+  }
+}
+
+template <class Tr>
+__device__ __forceinline__ typename Tr::S tree_elem_scaled(const void* const* p, int k, const TreeCode& tc, size_t e,
+                                                           ScaledFin<Tr> fin) {
+  using S = typename Tr::S;
+  using O = TreeOps<Tr, false>;
+  typename O::A acc[kTreeLevels][1], v[1];
+  for (int j = 0; j < k; ++j) {
+    v[0] = Tr::s_init(static_cast<const S*>(p[j])[e]);
+    tree_push_root<O, 1>(acc, v, tc.c[j], j == k - 1);
+  }
+  return fin.s(v[0]);
+}
+
+template <class Tr, int K, int U, class Sh>
+__device__ __forceinline__ void reduce_tree_body(const Srcs<(K > 0 ? K : FTAR_MAX_K)>& src, int kr,
+                                                 const TreeCode& tc, void* dst, size_t nvec, int head, int tail,
+                                                 ScaledFin<Tr> fin) {
+  using S = typename Tr::S;
+  using O = TreeOps<Tr, true>;
+  const int k = K > 0 ? K : kr;
+  constexpr int VE = 16 / sizeof(S);
+  const size_t tile_stride = (size_t)gridDim.x * (U * kThreads);
+  size_t v0 = (size_t)blockIdx.x * (U * kThreads) + threadIdx.x;
+
+  if (blockIdx.x == 0 && threadIdx.x < (unsigned)(head + tail)) {
+    const size_t e = threadIdx.x < (unsigned)head ? threadIdx.x : (size_t)head + nvec * VE + (threadIdx.x - head);
+    static_cast<S*>(dst)[e] = tree_elem_scaled<Tr>(src.p, k, tc, e, fin);
+  }
+  auto sp = [&](int j) { return reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head); };
+  u32x4* d = reinterpret_cast<u32x4*>(static_cast<S*>(dst) + head);
+  for (; v0 + (U - 1) * kThreads < nvec; v0 += tile_stride) {
+    typename O::A acc[kTreeLevels][U], v[U];
+    if constexpr (K > 0) {  // every source in flight before the first add
+      u32x4 x[K][U];
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int u = 0; u < U; ++u) x[j][u] = ld16<kNtLoads>(sp(j) + v0 + u * kThreads);
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = Tr::v_init(x[j][u]);
+        if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push_root<O, U>(acc, v, tc.c[j], j == K - 1);
+        else tree_push_root<O, U>(acc, v, Sh::code(j), j == K - 1);
+      }
+    } else {
+      for (int j = 0; j < k; ++j) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = Tr::v_init(ld16<kNtLoads>(sp(j) + v0 + u * kThreads));
+        tree_push_root<O, U>(acc, v, tc.c[j], j == k - 1);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) st16<kNtStores>(d + v0 + u * kThreads, fin.v(v[u]));
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {  // the one partial tile (if any)
+    const size_t vi = v0 + u * kThreads;
+    if (vi >= nvec) break;
+    typename O::A acc[kTreeLevels][1], v[1];
+    for (int j = 0; j < k; ++j) {
+      v[0] = Tr::v_init(ld16<kNtLoads>(sp(j) + vi));
+      tree_push_root<O, 1>(acc, v, tc.c[j], j == k - 1);
+    }
+    d[vi] = fin.v(v[0]);
+  }
+}
+template <class Tr, int K, int U, class Sh = RuntimeShape>
+__global__ void __launch_bounds__(kThreads)
+    reduce_tree_scaled_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, TreeCode tc, void* dst, size_t nvec,
+                              int head, int tail, typename Tr::SC scale) {
+  reduce_tree_body<Tr, K, U, Sh>(src, kr, tc, dst, nvec, head, tail, ScaledFin<Tr>{scale});
+}
+
+template <class Tr>
+__device__ __forceinline__ void reduce_tree_elem_body(const Srcs<FTAR_MAX_K>& src, int k, const TreeCode& tc,
+                                                      void* dst, size_t n, ScaledFin<Tr> fin) {
+  using S = typename Tr::S;
+  const size_t stride = (size_t)gridDim.x * kThreads;
+  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride)
+    static_cast<S*>(dst)[e] = tree_elem_scaled<Tr>(src.p, k, tc, e, fin);
+}
+template <class Tr>
+__global__ void __launch_bounds__(kThreads)
+    reduce_tree_elem_scaled_kernel(Srcs<FTAR_MAX_K> src, int k, TreeCode tc, void* dst, size_t n,
+                                   typename Tr::SC scale) {
+  reduce_tree_elem_body<Tr>(src, k, tc, dst, n, ScaledFin<Tr>{scale});
+}
+
+template <class Tr, int K, int U, int W, class Sh>
+__device__ __forceinline__ void reduce_tree_lds_body(const Srcs<K>& src, const TreeCode& tc, void* dst, size_t nvec,
+                                                     int head, int tail, ScaledFin<Tr> fin) {
+  using O = TreeOps<Tr, true>;
+  lds_staged<Tr, K, U, W, 2, true>(
+      src, dst, nvec, head, tail,
+      [&](auto get) {
+        typename O::A acc[kTreeLevels][1], v[1];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          v[0] = Tr::v_init(get(j));
+          if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push_root<O, 1>(acc, v, tc.c[j], j == K - 1);
+          else tree_push_root<O, 1>(acc, v, Sh::code(j), j == K - 1);
+        }
+        return fin.v(v[0]);
+      },
+      [&](size_t e) { return tree_elem_scaled<Tr>(src.p, K, tc, e, fin); });
+}
+template <class Tr, int K, int U, int W, class Sh>
+__global__ void __launch_bounds__(W * 64)
+    reduce_tree_lds_scaled_kernel(Srcs<K> src, TreeCode tc, void* dst, size_t nvec, int head, int tail,
+                                  typename Tr::SC scale) {
+  reduce_tree_lds_body<Tr, K, U, W, Sh>(src, tc, dst, nvec, head, tail, ScaledFin<Tr>{scale});
+}
+
 // ---------------------------------------------------------------------------
 // multi-segment copy: the peer-direct all-gather pulls every rank's final block
 // (over xGMI) into the caller's buffer in ONE launch.  Workgroup w copies
@@ -837,9 +1141,9 @@ __global__ void __launch_bounds__(kThreads) gather_logged_kernel(SegArgs a, int 
 // host-side launch
 // ---------------------------------------------------------------------------
 
-template <class Tr, int K, int U, bool NTL, bool NTS, int BS>
+template <class Tr, int K, int U, bool NTL, bool NTS, int BS, bool SC = false>
 hipError_t launch_cfg(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
-                      size_t max_blocks) {
+                      size_t max_blocks, double r = 1.0) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
   Srcs<KK> a{};
   for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
@@ -848,17 +1152,22 @@ hipError_t launch_cfg(const void* const* srcs, int k, void* dst, size_t nvec, in
   if (blocks == 0) blocks = 1;  // head/tail only
   if (max_blocks && blocks > max_blocks) blocks = max_blocks;  // grid-stride over the rest
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  FTAR_LAUNCH((reduce_vec_kernel<Tr, K, U, NTL, NTS, BS>), dim3((unsigned)blocks), dim3(BS), 0, s, a, k, dst,
-                     nvec, head, tail);
+  if constexpr (SC)
+    FTAR_LAUNCH((reduce_vec_scaled_kernel<Tr, K, U, NTL, NTS, BS>), dim3((unsigned)blocks), dim3(BS), 0, s, a, k, dst,
+                nvec, head, tail, (typename Tr::SC)r);
+  else
+    FTAR_LAUNCH((reduce_vec_kernel<Tr, K, U, NTL, NTS, BS>), dim3((unsigned)blocks), dim3(BS), 0, s, a, k, dst,
+                       nvec, head, tail);
   return hipGetLastError();
 }
 
-template <class Tr, int K>
-hipError_t launch_k(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s) {
+template <class Tr, int K, bool SC = false>
+hipError_t launch_k(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
+                    double r = 1.0) {
   if constexpr (K >= 2)
-    return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>>(srcs, dst, nvec, s, head, tail);
+    return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 2, true, SC>(srcs, dst, nvec, s, head, tail, r);
   else
-    return launch_cfg<Tr, K, kUnroll, kNtLoads, kNtStores, kVecThreads>(srcs, k, dst, nvec, head, tail, s, 0);
+    return launch_cfg<Tr, K, kUnroll, kNtLoads, kNtStores, kVecThreads, SC>(srcs, k, dst, nvec, head, tail, s, 0, r);
 }
 
 // Leaf codes of a nested fold with bottom-up widths shape[0..nlevels) over k
@@ -875,36 +1184,44 @@ bool make_tree_code(const int* shape, int nlevels, int k, TreeCode* tc) {
   return true;
 }
 
-template <class Tr, int K, int U, class Sh = RuntimeShape>
+template <class Tr, int K, int U, class Sh = RuntimeShape, bool SC = false>
 hipError_t launch_tree_k(const void* const* srcs, int k, const TreeCode& tc, void* dst, size_t nvec, int head,
-                         int tail, hipStream_t s) {
+                         int tail, hipStream_t s, double r = 1.0) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
   Srcs<KK> a{};
   for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
   size_t blocks = (nvec + (size_t)U * kThreads - 1) / ((size_t)U * kThreads);
   if (blocks == 0) blocks = 1;
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  FTAR_LAUNCH((reduce_tree_kernel<Tr, K, U, Sh>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
-                     nvec, head, tail);
+  if constexpr (SC)
+    FTAR_LAUNCH((reduce_tree_scaled_kernel<Tr, K, U, Sh>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
+                nvec, head, tail, (typename Tr::SC)r);
+  else
+    FTAR_LAUNCH((reduce_tree_kernel<Tr, K, U, Sh>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
+                       nvec, head, tail);
   return hipGetLastError();
 }
 
-template <class Tr, int K, class Sh = RuntimeShape>
+template <class Tr, int K, class Sh = RuntimeShape, bool SC = false>
 hipError_t launch_tree_lds(const void* const* srcs, const TreeCode& tc, void* dst, size_t nvec, int head, int tail,
-                           hipStream_t s) {
+                           hipStream_t s, double r = 1.0) {
   constexpr int U = kLdsTiles<Tr, K>, W = kLdsWaves<Tr, K>;
   Srcs<K> a{};
   for (int j = 0; j < K; ++j) a.p[j] = srcs[j];
   const size_t per_block = (size_t)W * U * 64;
   const size_t blocks = (nvec + per_block - 1) / per_block;
-  FTAR_LAUNCH((reduce_tree_lds_kernel<Tr, K, U, W, Sh>), dim3((unsigned)(blocks ? blocks : 1)), dim3(W * 64),
-                     0, s, a, tc, dst, nvec, head, tail);
+  if constexpr (SC)
+    FTAR_LAUNCH((reduce_tree_lds_scaled_kernel<Tr, K, U, W, Sh>), dim3((unsigned)(blocks ? blocks : 1)),
+                dim3(W * 64), 0, s, a, tc, dst, nvec, head, tail, (typename Tr::SC)r);
+  else
+    FTAR_LAUNCH((reduce_tree_lds_kernel<Tr, K, U, W, Sh>), dim3((unsigned)(blocks ? blocks : 1)), dim3(W * 64),
+                       0, s, a, tc, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
-template <class Tr>
+template <class Tr, bool SC = false>
 hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const int* shape, int nlevels, void* dst,
-                       size_t count, hipStream_t s, bool lds) {
+                       size_t count, hipStream_t s, bool lds, double r = 1.0) {
   using S = typename Tr::S;
   constexpr size_t VE = 16 / sizeof(S);
   const uintptr_t mis = reinterpret_cast<uintptr_t>(dst) & 15;
@@ -915,8 +1232,12 @@ hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const
     for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
     size_t blocks = (count + kThreads - 1) / kThreads;
     blocks = blocks > 8192 ? 8192 : blocks;
-    FTAR_LAUNCH((reduce_tree_elem_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
-                       count);
+    if constexpr (SC)
+      FTAR_LAUNCH((reduce_tree_elem_scaled_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
+                  count, (typename Tr::SC)r);
+    else
+      FTAR_LAUNCH((reduce_tree_elem_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
+                         count);
     return hipGetLastError();
   }
   size_t head = mis ? (16 - mis) / sizeof(S) : 0;
@@ -934,48 +1255,48 @@ hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const
   // v_cvt_pk_bf16_f32 (kLdsDeepBf16) on (2,2,2) and (2,2,2,2) too; its
   // runtime-coded folds still lose there and keep the register kernel.
   if (lds) {
-    if (is({2, 2})) return launch_tree_lds<Tr, 4, StaticShape<2, 2>>(srcs, tc, dst, nvec, h, tail, s);
-    if (is({2, 4})) return launch_tree_lds<Tr, 8, StaticShape<2, 4>>(srcs, tc, dst, nvec, h, tail, s);
-    if (is({4, 2})) return launch_tree_lds<Tr, 8, StaticShape<4, 2>>(srcs, tc, dst, nvec, h, tail, s);
-    if (is({4, 4})) return launch_tree_lds<Tr, 16, StaticShape<4, 4>>(srcs, tc, dst, nvec, h, tail, s);
+    if (is({2, 2})) return launch_tree_lds<Tr, 4, StaticShape<2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+    if (is({2, 4})) return launch_tree_lds<Tr, 8, StaticShape<2, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+    if (is({4, 2})) return launch_tree_lds<Tr, 8, StaticShape<4, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+    if (is({4, 4})) return launch_tree_lds<Tr, 16, StaticShape<4, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
   }
   if (lds && (sizeof(S) >= 4 || kLdsDeepBf16)) {
-    if (is({2, 2, 2})) return launch_tree_lds<Tr, 8, StaticShape<2, 2, 2>>(srcs, tc, dst, nvec, h, tail, s);
-    if (is({2, 2, 2, 2})) return launch_tree_lds<Tr, 16, StaticShape<2, 2, 2, 2>>(srcs, tc, dst, nvec, h, tail, s);
+    if (is({2, 2, 2})) return launch_tree_lds<Tr, 8, StaticShape<2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+    if (is({2, 2, 2, 2})) return launch_tree_lds<Tr, 16, StaticShape<2, 2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
   }
   if (lds && sizeof(S) >= 4) {
     switch (k) {  // other shapes: runtime leaf codes
-      case 4: return launch_tree_lds<Tr, 4>(srcs, tc, dst, nvec, h, tail, s);
-      case 6: return launch_tree_lds<Tr, 6>(srcs, tc, dst, nvec, h, tail, s);
-      case 8: return launch_tree_lds<Tr, 8>(srcs, tc, dst, nvec, h, tail, s);
-      case 9: return launch_tree_lds<Tr, 9>(srcs, tc, dst, nvec, h, tail, s);
-      case 12: return launch_tree_lds<Tr, 12>(srcs, tc, dst, nvec, h, tail, s);
-      case 16: return launch_tree_lds<Tr, 16>(srcs, tc, dst, nvec, h, tail, s);
+      case 4: return launch_tree_lds<Tr, 4, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+      case 6: return launch_tree_lds<Tr, 6, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+      case 8: return launch_tree_lds<Tr, 8, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+      case 9: return launch_tree_lds<Tr, 9, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+      case 12: return launch_tree_lds<Tr, 12, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+      case 16: return launch_tree_lds<Tr, 16, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
       default: break;
     }
-    return launch_tree_k<Tr, 0, 2>(srcs, k, tc, dst, nvec, h, tail, s);
+    return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
   }
   // registers (round 1; the A/B reference of ftar_debug_reduce_nested_lds)
-  if (is({2, 2})) return launch_tree_k<Tr, 4, 2, StaticShape<2, 2>>(srcs, k, tc, dst, nvec, h, tail, s);
-  if (is({2, 4})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 4>>(srcs, k, tc, dst, nvec, h, tail, s);
-  if (is({4, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<4, 2>>(srcs, k, tc, dst, nvec, h, tail, s);
-  if (is({2, 2, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 2, 2>>(srcs, k, tc, dst, nvec, h, tail, s);
-  if (is({4, 4})) return launch_tree_k<Tr, 16, 1, StaticShape<4, 4>>(srcs, k, tc, dst, nvec, h, tail, s);
-  if (is({2, 2, 2, 2})) return launch_tree_k<Tr, 16, 1, StaticShape<2, 2, 2, 2>>(srcs, k, tc, dst, nvec, h, tail, s);
+  if (is({2, 2})) return launch_tree_k<Tr, 4, 2, StaticShape<2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+  if (is({2, 4})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+  if (is({4, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<4, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+  if (is({2, 2, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+  if (is({4, 4})) return launch_tree_k<Tr, 16, 1, StaticShape<4, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+  if (is({2, 2, 2, 2})) return launch_tree_k<Tr, 16, 1, StaticShape<2, 2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
   switch (k) {  // other shapes: runtime leaf codes; 16 sources fit one vector per lane
-    case 4: return launch_tree_k<Tr, 4, 2>(srcs, k, tc, dst, nvec, h, tail, s);
-    case 6: return launch_tree_k<Tr, 6, 2>(srcs, k, tc, dst, nvec, h, tail, s);
-    case 8: return launch_tree_k<Tr, 8, 2>(srcs, k, tc, dst, nvec, h, tail, s);
-    case 16: return launch_tree_k<Tr, 16, 1>(srcs, k, tc, dst, nvec, h, tail, s);
-    default: return launch_tree_k<Tr, 0, 2>(srcs, k, tc, dst, nvec, h, tail, s);
+    case 4: return launch_tree_k<Tr, 4, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+    case 6: return launch_tree_k<Tr, 6, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+    case 8: return launch_tree_k<Tr, 8, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+    case 16: return launch_tree_k<Tr, 16, 1, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+    default: return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
   }
 }
 
 // HOT: the largest k with an unrolled LDS-staged kernel (fp32/bf16 16, the other types 8; 0 = k = 2
 // only); larger k take the runtime-k register kernel.  The other types gained 4-6 % at k = 8 on the
 // LDS kernel (tools/dtype_rates.py, profiles/r02/s4/dtype_rates*.log).
-template <class Tr, int HOT>
-hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hipStream_t s) {
+template <class Tr, int HOT, bool SC = false>
+hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0) {
   using S = typename Tr::S;
   constexpr size_t VE = 16 / sizeof(S);
   const uintptr_t mis = reinterpret_cast<uintptr_t>(dst) & 15;
@@ -986,7 +1307,11 @@ hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hi
     for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
     size_t blocks = (count + kThreads - 1) / kThreads;
     blocks = blocks > 8192 ? 8192 : blocks;
-    FTAR_LAUNCH((reduce_elem_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, dst, count);
+    if constexpr (SC)
+      FTAR_LAUNCH((reduce_elem_scaled_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, dst, count,
+                  (typename Tr::SC)r);
+    else
+      FTAR_LAUNCH((reduce_elem_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, dst, count);
     return hipGetLastError();
   }
   size_t head = mis ? (16 - mis) / sizeof(S) : 0;
@@ -997,13 +1322,14 @@ hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hi
   bool done = false;
   [&]<int... I>(std::integer_sequence<int, I...>) {  // k = 2 .. max(2, HOT), unrolled
     ((k == I + 2 && (I + 2 == 2 || I + 2 <= HOT)
-          ? (e = launch_k<Tr, (I + 2 <= (HOT > 2 ? HOT : 2) ? I + 2 : 2)>(srcs, k, dst, nvec, (int)head, (int)tail, s),
+          ? (e = launch_k<Tr, (I + 2 <= (HOT > 2 ? HOT : 2) ? I + 2 : 2), SC>(srcs, k, dst, nvec, (int)head, (int)tail,
+                                                                              s, r),
              done = true)
           : false),
      ...);
   }(std::make_integer_sequence<int, (HOT > 2 ? HOT : 2) - 1>{});
   if (done) return e;
-  return launch_k<Tr, 0>(srcs, k, dst, nvec, (int)head, (int)tail, s);
+  return launch_k<Tr, 0, SC>(srcs, k, dst, nvec, (int)head, (int)tail, s, r);
 }
 
 }  // namespace

@@ -20,6 +20,10 @@ size_t dtype_size(ftar_dtype_t dt) {
   return 0;
 }
 
+bool dtype_scalable(ftar_dtype_t dt) {
+  return dt == FTAR_FLOAT32 || dt == FTAR_FLOAT64 || dt == FTAR_BFLOAT16 || dt == FTAR_FLOAT16;
+}
+
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op) {
   if (dtype_size(dt) == 0) return false;
   switch (op) {
@@ -28,6 +32,7 @@ bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op) {
       return dt == FTAR_UINT8 || dt == FTAR_INT8 || dt == FTAR_UINT16 || dt == FTAR_INT16 || dt == FTAR_INT32 ||
              dt == FTAR_INT64;
     case FTAR_MAX: case FTAR_MIN: return dt != FTAR_BOOL;  // MPI defines no MAX / MIN on logical types either
+    case FTAR_AVG: return dtype_scalable(dt);  // the AllReduce entry points only (the engine: SUM + a scaled root)
   }
   return false;
 }
@@ -155,13 +160,57 @@ ftar_status_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t 
   return FTAR_SUCCESS;
 }
 
+namespace {
+// The scaled float sums (AVG's root folds, ftar_reduce_scaled): launch_reduce's SUM dispatch on the
+// *_scaled_kernel twins.  k = 1 is a scaled copy (the runtime-k register kernel, or the element kernel).
+// A one-round ring fold (round_each, k > 2) rounds before each add instead of after it, so the last sum
+// reaches the finisher unrounded, as the staged ring's last hop (a plain k = 2 fold) hands it over.
+template <class Tr, int HOT>
+hipError_t tr_scaled(bool lds, const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r) {
+  return lds ? launch_tr<Tr, HOT, true>(srcs, k, dst, count, s, r) : launch_tr<Tr, 0, true>(srcs, k, dst, count, s, r);
+}
+ftar_status_t launch_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, hipStream_t s,
+                            bool round_each, const int* shape, int nlevels, bool lds, double r) {
+  hipError_t e = hipErrorInvalidValue;
+  if (nlevels > 1 && k > 1) {
+    TreeCode tc;
+    if (!shape || !make_tree_code(shape, nlevels, k, &tc)) return FTAR_ERR_INVALID_ARG;
+    switch (dt) {
+      case FTAR_FLOAT32: e = launch_tree<F32Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
+      case FTAR_FLOAT64: e = launch_tree<F64Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, false, r); break;
+      case FTAR_FLOAT16: e = launch_tree<F16Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
+      default: e = launch_tree<BF16Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
+    }
+    FTAR_CHECK_HIP(e);
+    return FTAR_SUCCESS;
+  }
+  switch (dt) {
+    case FTAR_FLOAT32: e = tr_scaled<F32Sum, 16>(lds, srcs, k, dst, count, s, r); break;
+    case FTAR_FLOAT64: e = tr_scaled<F64Sum, 8>(lds, srcs, k, dst, count, s, r); break;
+    case FTAR_FLOAT16:
+      e = round_each && k > 2 ? tr_scaled<F16SumHopPre, 16>(lds, srcs, k, dst, count, s, r)
+                              : tr_scaled<F16Sum, 16>(lds, srcs, k, dst, count, s, r);
+      break;
+    default:
+      e = round_each && k > 2 ? tr_scaled<BF16SumHopPre, 16>(lds, srcs, k, dst, count, s, r)
+                              : tr_scaled<BF16Sum, 16>(lds, srcs, k, dst, count, s, r);
+      break;
+  }
+  FTAR_CHECK_HIP(e);
+  return FTAR_SUCCESS;
+}
+}  // namespace
+
 ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                            hipStream_t s, bool round_each, const int* shape, int nlevels, bool lds) {
+                            hipStream_t s, bool round_each, const int* shape, int nlevels, bool lds,
+                            const double* scale) {
   if (k < 1 || k > FTAR_MAX_K || !srcs || !dst) return FTAR_ERR_INVALID_ARG;
-  if (!dtype_op_supported(dt, op)) return FTAR_ERR_UNSUPPORTED;
+  if (op == FTAR_AVG || !dtype_op_supported(dt, op)) return FTAR_ERR_UNSUPPORTED;  // AVG: the engine's SUM + scale
+  if (scale && (op != FTAR_SUM || !dtype_scalable(dt))) return FTAR_ERR_UNSUPPORTED;
   if (count == 0) return FTAR_SUCCESS;
   for (int j = 0; j < k; ++j)
     if (!srcs[j]) return FTAR_ERR_INVALID_ARG;
+  if (scale) return launch_scaled(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale);
   if (k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)
     return launch_copy(srcs[0], dst, count * dtype_size(dt), s);
   hipError_t e = hipErrorInvalidValue;
@@ -209,6 +258,7 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
     break;
   case FTAR_MAX: e = tr_min_max<true>(dt, lds, srcs, k, dst, count, s); break;
   case FTAR_MIN: e = tr_min_max<false>(dt, lds, srcs, k, dst, count, s); break;
+  case FTAR_AVG: break;  // refused above
   }
   FTAR_CHECK_HIP(e);
   return FTAR_SUCCESS;

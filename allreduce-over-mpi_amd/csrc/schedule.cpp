@@ -412,6 +412,19 @@ Stage direct_tree_stage(const Topology& t, size_t P, size_t me, size_t count) {
   st.reduces.push_back(std::move(it));
   return st;
 }
+// After the reduce-scatter this rank owns one block (block r on trees, lonely layouts included; block
+// (r+1) mod P on the ring): the last item in stage order that writes that block's range produced its final
+// value -- the block's root fold, where AVG scales.  Independent of the op: the plan caches need no new key.
+void mark_root(Plan* p, bool ring) {
+  const size_t P = (size_t)p->nranks, me = (size_t)p->rank;
+  const Range mine = block_range(ring ? (me + 1) % P : me, P, p->count);
+  if (!mine.len) return;
+  ReduceItem* last = nullptr;
+  for (Stage& st : p->stages)
+    for (ReduceItem& r : st.reduces)
+      if (r.off < mine.actual + mine.len && mine.actual < r.off + r.len) last = &r;
+  if (last && last->off == mine.actual && last->len == mine.len) last->root = true;
+}
 }  // namespace
 
 ftar_status_t build_plan(const Topology& t, int nranks, int rank, size_t count, Plan* out, Form form) {
@@ -556,6 +569,7 @@ ftar_status_t build_plan(const Topology& t, int nranks, int rank, size_t count, 
     p.max_k = max_k;
   }
   p.scratch_half = half;
+  mark_root(&p, t.ring);
   *out = std::move(p);
   return FTAR_SUCCESS;
 }
@@ -606,7 +620,7 @@ std::string Plan::json() const {
     for (size_t j = 0; j < s.reduces.size(); ++j) {
       const ReduceItem& r = s.reduces[j];
       os << (j ? "," : "") << "{\"off\":" << r.off << ",\"len\":" << r.len << ",\"round_each\":"
-         << (r.round_each ? 1 : 0) << ",\"shape\":[";
+         << (r.round_each ? 1 : 0) << ",\"root\":" << (r.root ? 1 : 0) << ",\"shape\":[";
       for (size_t q = 0; q < r.shape.size(); ++q) os << (q ? "," : "") << r.shape[q];
       os << "],\"srcs\":[";
       for (size_t q = 0; q < r.srcs.size(); ++q)

@@ -413,6 +413,10 @@ class RcclTransport final : public Transport {
       case FTAR_SUM: o = ncclSum; break;
       case FTAR_MAX: o = ncclMax; break;
       case FTAR_MIN: o = ncclMin; break;
+      case FTAR_AVG:  // RCCL's mean: integers too, by its own rules; ftar's AVG is the float dtypes'
+        if (!dtype_scalable(dt)) return FTAR_ERR_UNSUPPORTED;
+        o = ncclAvg;
+        break;
       default: return FTAR_ERR_UNSUPPORTED;
     }
     FTAR_CHECK_NCCL(ncclAllReduce(send ? send : recv, recv, count, t, o, comm_, s));

@@ -46,7 +46,7 @@ MPI_DTYPE = {"MPI_UINT8_T": 0, "MPI_INT8_T": 1, "MPI_UINT16_T": 2, "MPI_INT16_T"
              "MPI_INT64_T": 5, "MPI_LONG_LONG": 5, "MPI_LONG_LONG_INT": 5, "MPI_FLOAT": 6, "MPI_DOUBLE": 7,
              "MPI_C_BOOL": 8}
 # "max" / "min" (and "f16" above) are ftar extensions: the MPI names stay the reference's list
-OP = {"sum": 0, "band": 1, "max": 2, "min": 3, "MPI_SUM": 0, "MPI_BAND": 1}
+OP = {"sum": 0, "band": 1, "max": 2, "min": 3, "avg": 4, "MPI_SUM": 0, "MPI_BAND": 1}  # avg: no MPI_ alias
 ALLGATHER = {"stages": 0, "collective": 1, "direct": 2}   # ftar_allgather_t
 _AG_NAME = {v: k for k, v in ALLGATHER.items()}
 REDUCE_SCATTER = {"stages": 0, "direct": 1}                 # ftar_reduce_scatter_t
@@ -124,6 +124,8 @@ _lib.ftar_dtype_size.restype = _sz
 _lib.ftar_dtype_size.argtypes = [_int]
 _lib.ftar_reduce.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, _int, _vp]
 _lib.ftar_reduce_nested.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, _int, ctypes.POINTER(_int), _int, _vp]
+_lib.ftar_reduce_scaled.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, ctypes.c_double, ctypes.POINTER(_int),
+                                    _int, _vp]
 _lib.ftar_topo_parse.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _int, ctypes.POINTER(Topo)]
 _lib.ftar_topo_from_env.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
 _lib.ftar_topo_choose.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
@@ -288,11 +290,19 @@ def last_kernel():
 
 
 # ---- L3: one-device reduce ----------------------------------------------------
-def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None):
+def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None, scale=None):
     """dst[i] = srcs[0][i] op srcs[1][i] op ... (left to right), enqueued on `stream`.
-    shape=[w0, w1, ...]: nested fold of the sources in depth-first leaf order (ftar_reduce_nested)."""
+    shape=[w0, w1, ...]: nested fold of the sources in depth-first leaf order (ftar_reduce_nested).
+    scale=s (op "sum" of f32, f64, bf16, f16): the fold's accumulator times s before its one rounding
+    (ftar_reduce_scaled: the root fold of an AVG AllReduce, s = 1 / P)."""
     arr = (_vp * len(srcs))(*[_ptr(s) for s in srcs])
-    if shape is None:
+    if scale is not None:
+        if _op(op) != OP["sum"]:
+            raise ValueError("scale goes with op='sum'")
+        sh = (_int * max(1, len(shape or ())))(*(shape or ()))
+        _check(_lib.ftar_reduce_scaled(arr, len(srcs), _ptr(dst), count, _dt(dtype), float(scale), sh,
+                                       len(shape or ()), _stream(stream)), "ftar_reduce_scaled")
+    elif shape is None:
         _check(_lib.ftar_reduce(arr, len(srcs), _ptr(dst), count, _dt(dtype), _op(op), _stream(stream)),
                "ftar_reduce")
     else:

@@ -3,10 +3,20 @@
 The data-parallel caller of the hot path: DDP packs gradients into buckets and hands each bucket to a hook
 once its gradients are ready; the hook below reduces the bucket in place with ftar_allreduce on the stream the
 backward pass runs on (the FlexTree schedule of FT_TOPO / FT_LONELY or `topo`, else the cost model; RCCL p2p
-over xGMI, the reduce kernel on ftar's own stream); the bucket is divided by the world size first, as DDP's own
-allreduce hook does (so the mean rounds as DDP's does and keeps its overflow headroom).  No host
-synchronisation: the AllReduce and every later use of the bucket are ordered after the division by that
-stream.
+over xGMI, the reduce kernel on ftar's own stream).  No host synchronisation: the AllReduce and every later
+use of the bucket are ordered on that stream.
+
+The mean, two ways (HookState's `average`):
+
+  * "divide" (the default): the bucket is divided by the world size first, as DDP's own allreduce hook does,
+    then summed, so the mean rounds as DDP's does and keeps its overflow headroom in every form.  The division
+    is a torch kernel of its own: one more read and write of the whole bucket, and one more rounding per
+    element of an fp16 / bf16 bucket.
+  * "fused": no division; the AllReduce runs op="avg" (FTAR_AVG, include/ftar.h), which multiplies by 1 / P
+    inside the last fold of each block, where the sum still sits in its fp32 accumulator.  In the one-round
+    forms (the default) the P copies are summed in fp32, scaled and rounded once: one rounding instead of
+    P + 1, and an fp16 mean stays finite where the fp16 sum would be inf.  The staged 16-bit forms round
+    partial sums between hops, so there a partial sum can overflow: they lose the pre-division's headroom.
 
     comm = ftar.dist.init_comm()                       # one rank per GPU, RCCL over the DDP process group's ids
     model = DistributedDataParallel(model, device_ids=[local_rank])
@@ -27,22 +37,29 @@ import ftar
 
 
 class HookState:
-    """What the hook needs: the ftar communicator, and optionally a fixed topology (FT_TOPO syntax)."""
+    """What the hook needs: the ftar communicator, optionally a fixed topology (FT_TOPO syntax), and how the
+    mean is taken: average="divide" (div_ by the world size, then op="sum") or "fused" (op="avg": no division
+    pass; rounded once in the one-round forms and no overflow there, but the staged 16-bit forms round partial
+    sums between hops and lose the pre-division's headroom)."""
 
-    def __init__(self, comm, topo=None, lonely=0):
-        self.comm, self.topo, self.lonely = comm, topo, lonely
+    def __init__(self, comm, topo=None, lonely=0, average="divide"):
+        if average not in ("divide", "fused"):
+            raise ValueError(f"average must be 'divide' or 'fused', not {average!r}")
+        self.comm, self.topo, self.lonely, self.average = comm, topo, lonely, average
         self.calls = 0
 
 
 def allreduce_hook(state, bucket):
     """DDP comm hook: the bucket / world size (first, as torch's default hook divides before it reduces), then
-    its in-place FlexTree AllReduce; returns a completed future whose tensor the reducer copies back into the
-    gradients on the same stream."""
+    its in-place FlexTree AllReduce -- or, with average="fused", the AllReduce alone with op="avg"; returns a
+    completed future whose tensor the reducer copies back into the gradients on the same stream."""
     t = bucket.buffer()
     stream = torch.cuda.current_stream(t.device)
-    t.div_(state.comm.nranks)
-    state.comm.allreduce(None, t, t.numel(), ftar._dt(str(t.dtype)), "sum", topo_=state.topo, lonely=state.lonely,
-                         stream=stream)
+    fused = state.average == "fused"
+    if not fused:
+        t.div_(state.comm.nranks)
+    state.comm.allreduce(None, t, t.numel(), ftar._dt(str(t.dtype)), "avg" if fused else "sum", topo_=state.topo,
+                         lonely=state.lonely, stream=stream)
     state.calls += 1
     fut = torch.futures.Future(devices=[t.device])
     fut.set_result(t)

@@ -60,17 +60,18 @@ typedef enum {
   FTAR_SUM = 0,  /* MPI_SUM */
   FTAR_BAND = 1, /* MPI_BAND (integer types only, as in the reference) */
   FTAR_MAX = 2,  /* extension: every dtype but FTAR_BOOL (see below) */
-  FTAR_MIN = 3   /* extension: every dtype but FTAR_BOOL */
+  FTAR_MIN = 3,  /* extension: every dtype but FTAR_BOOL */
+  FTAR_AVG = 4   /* extension: the mean, f32 f64 bf16 f16, the AllReduce entry points only (see below) */
 } ftar_op_t;
 
 /* Which (dtype, op) pairs run; the rest return FTAR_ERR_UNSUPPORTED before any device work.
  *
- *                  SUM   BAND   MAX   MIN
- *   u8 i8 u16 i16   x     x      x     x
- *   i32 i64         x     x      x     x
- *   f32 f64         x     -      x     x
- *   bf16 f16        x     -      x     x
- *   bool            x(OR) -      -     -      (MPI defines no MAX/MIN on logical types either)
+ *                  SUM   BAND   MAX   MIN   AVG
+ *   u8 i8 u16 i16   x     x      x     x     -
+ *   i32 i64         x     x      x     x     -
+ *   f32 f64         x     -      x     x     x     (AVG: ftar_allreduce, _group, _host, _host_group;
+ *   bf16 f16        x     -      x     x     x      ftar_reduce / ftar_reduce_nested refuse it)
+ *   bool            x(OR) -      -     -     -     (MPI defines no MAX/MIN on logical types either)
  *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
  * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
@@ -83,6 +84,21 @@ typedef enum {
  * flushed, a non-NaN result is bit for bit one of the sources, and any NaN source makes the lane NaN
  * (payload unspecified).  Both are exact, associative and commutative, so every topology, form, piece size
  * and buffer kind gives the same bits, and a nested shape (ftar_reduce_nested) has no effect on them.
+ *
+ * AVG (ncclAvg, torch's ReduceOp.AVG) is SUM's schedule, unchanged, except at the root fold of each block:
+ * the one reduce that produces the block's final value on the rank that owns it after the reduce-scatter.
+ * That fold finishes as out = round_to_dtype(A x r): A is its accumulator before its rounding (fp32 for
+ * bf16 / f16, the dtype itself for f32 / f64) and r = 1.0f / (float)P (f64: 1.0 / (double)P) -- one
+ * multiply by the reciprocal (as NCCL and torch's scalar division on the GPU do; not a division), correctly
+ * rounded in the accumulator's precision, subnormal products kept; for the 16-bit floats the root's single
+ * round to nearest even follows.  Inner nodes and earlier hops round exactly as under SUM; P = 1 is SUM's
+ * copy; a lane with a NaN or an inf - inf stays NaN (payload unspecified).  For one topology every form
+ * (stages, direct, collective all-gather, peer read, peer write), piece size and buffer kind gives the same
+ * bits.  In the one-round forms a 16-bit mean is therefore summed in fp32, scaled and rounded once: an fp16
+ * mean stays finite where the fp16 sum is inf.  The staged forms round partial sums between hops, where a
+ * partial sum can still overflow.  Integers and bool return FTAR_ERR_UNSUPPORTED before any device work.
+ * A one-device reduce has no P: ftar_reduce and ftar_reduce_nested refuse FTAR_AVG (FTAR_ERR_UNSUPPORTED,
+ * before touching a pointer); the one-device surface is ftar_reduce_scaled.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
@@ -134,6 +150,14 @@ ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t coun
  * ftar_reduce's (the flat kernel runs).  nlevels <= 1 is ftar_reduce. */
 ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  ftar_op_t op, const int* shape, int nlevels, void* stream);
+/* Scaled SUM (extension; AVG's root fold on one device) of f32, f64, bf16 or f16: flat for nlevels <= 1,
+ * nested as ftar_reduce_nested otherwise, finishing as dst = round_to_dtype(A x scale) -- A the fold's
+ * accumulator before its one rounding (fp32 for bf16 / f16; a nested fold's root, its inner nodes rounded
+ * as ever), scale cast to float unless the dtype is f64, one correctly rounded multiply, subnormal products
+ * kept.  k == 1 is a scaled copy; dst may alias srcs[0].  A non-finite scale returns FTAR_ERR_INVALID_ARG,
+ * other dtypes FTAR_ERR_UNSUPPORTED, both before any device work. */
+ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
+                                 double scale, const int* shape, int nlevels, void* stream);
 
 /* ---- topology ------------------------------------------------------------
  * ftar_topo_parse: FT_TOPO / FT_LONELY strings (NULL = unset) for nranks.
@@ -435,9 +459,9 @@ ftar_status_t ftar_comm_get_host_chunk_bytes(ftar_comm_t comm, size_t* bytes);
  * RCCL's own ncclAllReduce on the communicator's RCCL comm (ring/tree of the
  * vendor library, reduction inside RCCL): the yardstick bench.py reports next
  * to ftar at N > 1.  FTAR_ERR_UNSUPPORTED on local (in-process) groups, for
- * the types RCCL lacks (u16, i16, bool) and for BAND.  SUM, MAX and MIN map to
- * ncclSum / ncclMax / ncclMin, fp16 to ncclFloat16: the arithmetic is RCCL's,
- * so its NaN and signed-zero rules for max / min may differ from ftar's. */
+ * the types RCCL lacks (u16, i16, bool) and for BAND.  SUM, MAX, MIN and AVG map to
+ * ncclSum / ncclMax / ncclMin / ncclAvg, fp16 to ncclFloat16: the arithmetic is RCCL's,
+ * so its NaN and signed-zero rules for max / min, and where it rounds a mean, may differ from ftar's. */
 ftar_status_t ftar_rccl_allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dtype, ftar_op_t op,
                                   ftar_comm_t comm, void* stream);
 /* xGMI calibration (collective; every rank calls it): GB/s seen by this rank

@@ -3,8 +3,9 @@
 (k sources + destination) sets of 256 MiB buffers; GB/s of (k+1) x 256 MiB algorithmic bytes, median of
 interleaved rounds, with the slowest and fastest round next to it (the run's own spread: the margin when
 one (dtype, op) is judged against another of the same width).  --op takes a list; pairs the library
-refuses (band on floats, max on bool) are skipped.
-python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f16,f64,i32,i16,u8,bool] [--op sum,max,min]"""
+refuses (band on floats, max on bool) are skipped.  "scaled" is ftar_reduce_scaled (the sum times 1 / k before
+its rounding: AVG's root fold), to be read against "sum" of the same dtype and k in the same run.
+python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f16,f64,i32,i16,u8,bool] [--op sum,max,min,scaled]"""
 import argparse
 import json
 import os
@@ -19,7 +20,7 @@ import ftar  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--ks", default="2,8")
 ap.add_argument("--dtypes", default="f32,bf16,f64,i64,i32,i16,u8,bool")
-ap.add_argument("--op", default="sum", help="one op or a comma list: sum,band,max,min")
+ap.add_argument("--op", default="sum", help="one op or a comma list: sum,band,max,min,scaled")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=8)
 a = ap.parse_args()
@@ -37,7 +38,10 @@ for _ in range(a.rounds):
         for k in ks:
             def launch(i):
                 s = bufs[i % S]
-                ftar.reduce(s[:k], s[max(ks)], n, d, op, stream=stream)
+                if op == "scaled":
+                    ftar.reduce(s[:k], s[max(ks)], n, d, "sum", stream=stream, scale=1.0 / k)
+                else:
+                    ftar.reduce(s[:k], s[max(ks)], n, d, op, stream=stream)
             if (d, op) in refused:
                 continue
             try:
