@@ -30,8 +30,8 @@
 //   * extensions (no reference): bf16 and fp16 sums = fp32 accumulate + one RNE per
 //     reduce; MAX / MIN = signed or unsigned integer compare, IEEE 754-2019
 //     maximum / minimum on floats (exact: every fold order gives the same bits); the scaled float sums
-//     (AVG's root fold, ftar_reduce_scaled): the accumulator times r before the fold's one rounding, on
-//     *_scaled_kernel twins of the fold kernels (ScaledFin below).
+//     (AVG's root fold, ftar_reduce_scaled): the accumulator times r before the fold's one rounding --
+//     one body per kernel family, two finishes (PlainFin / ScaledFin below).
 #pragma once
 // Internal: the reduce kernels, their traits and launchers, included by reduce_kernels.hip (the
 // production dispatch, libftar.so) and bench_kernels.hip (the A/B harness, libftar_bench.so);
@@ -54,6 +54,15 @@ inline thread_local const void* g_last_kernel = nullptr;
   do {                                                                   \
     ::ftar::g_last_kernel = reinterpret_cast<const void*>(KERNEL);       \
     hipLaunchKernelGGL(KERNEL, __VA_ARGS__);                             \
+  } while (0)
+// A fold family in either finish (PlainFin / ScaledFin below): NAME_kernel<TARGS>(args...) or, with SC, its
+// twin NAME_scaled_kernel<TARGS>(args..., SCALE).  TARGS is parenthesised; only the kernel launched is
+// instantiated, so traits without a scaled finish never name one.
+#define FTAR_TARGS(...) __VA_ARGS__
+#define FTAR_LAUNCH_FIN(SC, SCALE, NAME, TARGS, ...)                                             \
+  do {                                                                                           \
+    if constexpr (SC) FTAR_LAUNCH((NAME##_scaled_kernel<FTAR_TARGS TARGS>), __VA_ARGS__, SCALE); \
+    else FTAR_LAUNCH((NAME##_kernel<FTAR_TARGS TARGS>), __VA_ARGS__);                            \
   } while (0)
 
 namespace {
@@ -431,24 +440,38 @@ struct BF16MinMax {
   }
 };
 
-// The scaled finish (AVG's root fold, ftar_reduce_scaled; the float sums): out = round_to_dtype(A * r), one
-// multiply in the accumulator's precision (fp32 for bf16 / fp16; subnormal products kept), then the
-// fold's single rounding.  The scale is a kernarg of the *_scaled_kernel twins below: instantiations of
-// their own, next to the kernels every other op launches, whose code is not shared with them and so
-// compiles to what it was.
+// The finish of a fold: how the accumulator becomes the stored value.  One *_body per kernel family, two finishes:
+//   PlainFin: the trait's own v_fin / s_fin (every op and dtype);
+//   ScaledFin (AVG's root fold, ftar_reduce_scaled; the float sums): out = round_to_dtype(A * r), one multiply
+//     in the accumulator's precision (fp32 for bf16 / fp16; subnormal products kept), then the fold's single
+//     rounding.  A nested fold hands it the root unrounded (kRawRoot, tree_push).
+// A family's two __global__ kernels, NAME_kernel(args) and NAME_scaled_kernel(args, scale), are two-line
+// wrappers over its body: profiles and tools key on those names and argument lists.  (The register kernels
+// reduce_vec_kernel and reduce_tree_kernel are the exception, see there: only their scaled kernel has a body.)
+template <class Tr>
+struct PlainFin {
+  static constexpr bool kRawRoot = false;
+  __device__ static typename Tr::S s(typename Tr::SA a) { return Tr::s_fin(a); }
+  __device__ static u32x4 v(typename Tr::VA a) { return Tr::v_fin(a); }
+};
 template <class Tr>
 struct ScaledFin {
+  static constexpr bool kRawRoot = true;
   typename Tr::SC r;
   __device__ typename Tr::S s(typename Tr::SA a) const { return Tr::s_fin(Tr::s_scale(a, r)); }
   __device__ u32x4 v(typename Tr::VA a) const { return Tr::v_fin(Tr::v_scale(a, r)); }
 };
-// Host side: a launcher's template argument SC = true, with the scale r (cast to Tr::SC at the launch), launches
-// the scaled twin; each twin is a *_body (the parent kernel's loop with `fin` as its finish) and its __global__.
 
 template <int K>
 struct Srcs {
   const void* p[K];
 };
+template <int K>
+Srcs<K> pack_srcs(const void* const* srcs, int k) {
+  Srcs<K> a{};
+  for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
+  return a;
+}
 
 // ---------------------------------------------------------------------------
 // vector kernel: K sources (K == 0: runtime k <= FTAR_MAX_K), U vectors per lane.
@@ -517,8 +540,11 @@ __global__ void __launch_bounds__(BS)
   }
 }
 
-// The scaled twin: reduce_vec_kernel with a ScaledFin finish (its own instantiation; the kernel above is
-// what every other op launches, untouched).
+// The scaled twin: reduce_vec_kernel's loop again, with a ScaledFin finish.  The two register families (this one
+// and reduce_tree_kernel) keep two copies of their loop -- a fix to one goes into both.  Behind a shared body
+// the compiler optimises the body before it inlines it into the kernel and hoists every kernarg pointer load
+// to the kernel's entry: the static-K instantiations (the A/B variants of bench_kernels.hip) came out
+// different, a dozen of them with more VGPRs and an occupancy step lost (tools/asm_diff.py, profiles/README.md).
 template <class Tr, int K, int U, bool NTL, bool NTS, int BS>
 __device__ __forceinline__ void reduce_vec_body(const Srcs<(K > 0 ? K : FTAR_MAX_K)>& src, int kr, void* dst,
                                                 size_t nvec, int head, int tail, ScaledFin<Tr> fin) {
@@ -653,28 +679,9 @@ __device__ __forceinline__ void lds_staged(const Srcs<K>& src, void* dst, size_t
   }
 }
 
-template <class Tr, int K, int U, int W, int AUX, bool PROG>
-__global__ void __launch_bounds__(W * 64)
-    reduce_lds_kernel(Srcs<K> src, void* dst, size_t nvec, int head, int tail) {
-  using S = typename Tr::S;
-  lds_staged<Tr, K, U, W, AUX, PROG>(
-      src, dst, nvec, head, tail,
-      [](auto get) {
-        typename Tr::VA a = Tr::v_init(get(0));
-#pragma unroll
-        for (int j = 1; j < K; ++j) a = Tr::v_comb(a, get(j));
-        return Tr::v_fin(a);
-      },
-      [&](size_t e) {
-        typename Tr::SA a = Tr::s_init(static_cast<const S*>(src.p[0])[e]);
-        for (int j = 1; j < K; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
-        return Tr::s_fin(a);
-      });
-}
-
-template <class Tr, int K, int U, int W, int AUX, bool PROG>
+template <class Tr, int K, int U, int W, int AUX, bool PROG, class Fin>
 __device__ __forceinline__ void reduce_lds_body(const Srcs<K>& src, void* dst, size_t nvec, int head, int tail,
-                                                ScaledFin<Tr> fin) {
+                                                Fin fin) {
   using S = typename Tr::S;
   lds_staged<Tr, K, U, W, AUX, PROG>(
       src, dst, nvec, head, tail,
@@ -692,6 +699,11 @@ __device__ __forceinline__ void reduce_lds_body(const Srcs<K>& src, void* dst, s
 }
 template <class Tr, int K, int U, int W, int AUX, bool PROG>
 __global__ void __launch_bounds__(W * 64)
+    reduce_lds_kernel(Srcs<K> src, void* dst, size_t nvec, int head, int tail) {
+  reduce_lds_body<Tr, K, U, W, AUX, PROG>(src, dst, nvec, head, tail, PlainFin<Tr>{});
+}
+template <class Tr, int K, int U, int W, int AUX, bool PROG>
+__global__ void __launch_bounds__(W * 64)
     reduce_lds_scaled_kernel(Srcs<K> src, void* dst, size_t nvec, int head, int tail, typename Tr::SC scale) {
   reduce_lds_body<Tr, K, U, W, AUX, PROG>(src, dst, nvec, head, tail, ScaledFin<Tr>{scale});
 }
@@ -702,35 +714,18 @@ hipError_t launch_lds(const void* const* srcs, void* dst, size_t nvec, hipStream
   if constexpr (W * U * K > 160) {
     return hipErrorInvalidValue;
   } else {
-    Srcs<K> a{};
-    for (int j = 0; j < K; ++j) a.p[j] = srcs[j];
     const size_t per_block = (size_t)W * U * 64;
     const size_t blocks = (nvec + per_block - 1) / per_block;
     const dim3 grid((unsigned)(blocks ? blocks : 1));
-    if constexpr (SC)
-      FTAR_LAUNCH((reduce_lds_scaled_kernel<Tr, K, U, W, AUX, PROG>), grid, dim3(W * 64), 0, s, a, dst, nvec, head,
-                  tail, (typename Tr::SC)r);
-    else
-      FTAR_LAUNCH((reduce_lds_kernel<Tr, K, U, W, AUX, PROG>), grid, dim3(W * 64), 0, s, a, dst, nvec, head, tail);
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_lds, (Tr, K, U, W, AUX, PROG), grid, dim3(W * 64), 0, s,
+                    pack_srcs<K>(srcs, K), dst, nvec, head, tail);
     return hipGetLastError();
   }
 }
 
 // element-wise fallback for sources not co-aligned with dst
-template <class Tr>
-__global__ void __launch_bounds__(kThreads)
-    reduce_elem_kernel(Srcs<FTAR_MAX_K> src, int k, void* dst, size_t n) {
-  using S = typename Tr::S;
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride) {
-    typename Tr::SA a = Tr::s_init(static_cast<const S*>(src.p[0])[e]);
-    for (int j = 1; j < k; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
-    static_cast<S*>(dst)[e] = Tr::s_fin(a);
-  }
-}
-template <class Tr>
-__device__ __forceinline__ void reduce_elem_body(const Srcs<FTAR_MAX_K>& src, int k, void* dst, size_t n,
-                                                 ScaledFin<Tr> fin) {
+template <class Tr, class Fin>
+__device__ __forceinline__ void reduce_elem_body(const Srcs<FTAR_MAX_K>& src, int k, void* dst, size_t n, Fin fin) {
   using S = typename Tr::S;
   const size_t stride = (size_t)gridDim.x * kThreads;
   for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride) {
@@ -738,6 +733,11 @@ __device__ __forceinline__ void reduce_elem_body(const Srcs<FTAR_MAX_K>& src, in
     for (int j = 1; j < k; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
     static_cast<S*>(dst)[e] = fin.s(a);
   }
+}
+template <class Tr>
+__global__ void __launch_bounds__(kThreads)
+    reduce_elem_kernel(Srcs<FTAR_MAX_K> src, int k, void* dst, size_t n) {
+  reduce_elem_body<Tr>(src, k, dst, n, PlainFin<Tr>{});
 }
 template <class Tr>
 __global__ void __launch_bounds__(kThreads)
@@ -810,10 +810,14 @@ struct TreeOps<Tr, false> {
   __device__ static A rnd(A a) { return Tr::s_rnd(a); }
 };
 
-// push leaf values v[0..U) (one per vector slot) up the tree; on the last leaf
-// v ends up holding the root
-template <class O, int U>
-__device__ __forceinline__ void tree_push(typename O::A (&acc)[kTreeLevels][U], typename O::A (&v)[U], unsigned code) {
+// push leaf values v[0..U) (one per vector slot) up the tree; on the last leaf v ends up holding the
+// root.  Inner nodes are rounded as they close (the staged schedule stores them in the dtype); RAW (the
+// finish's kRawRoot) leaves the root as its level's accumulator holds it, unrounded, for the finish to scale
+// and round once: the last leaf (`last`) completes every level (done = L), so the root is the node that
+// closes at level done - 1.  Without RAW `last` is dead and compiles to nothing.
+template <bool RAW, class O, int U>
+__device__ __forceinline__ void tree_push(typename O::A (&acc)[kTreeLevels][U], typename O::A (&v)[U], unsigned code,
+                                          bool last) {
   const unsigned done = code & 7u;
 #pragma unroll
   for (int l = 0; l < kTreeLevels; ++l) {
@@ -821,23 +825,30 @@ __device__ __forceinline__ void tree_push(typename O::A (&acc)[kTreeLevels][U], 
 #pragma unroll
     for (int u = 0; u < U; ++u) acc[l][u] = fresh ? v[u] : O::add(acc[l][u], v[u]);
     if (done <= (unsigned)l) break;
+    const bool root = RAW && last && done == (unsigned)l + 1;
 #pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = O::rnd(acc[l][u]);
+    for (int u = 0; u < U; ++u) v[u] = root ? acc[l][u] : O::rnd(acc[l][u]);
   }
 }
 
-template <class Tr>
-__device__ __forceinline__ typename Tr::S tree_elem(const void* const* p, int k, const TreeCode& tc, size_t e) {
+template <class Tr, class Fin>
+__device__ __forceinline__ typename Tr::S tree_elem(const void* const* p, int k, const TreeCode& tc, size_t e,
+                                                    Fin fin) {
   using S = typename Tr::S;
   using O = TreeOps<Tr, false>;
   typename O::A acc[kTreeLevels][1], v[1];
   for (int j = 0; j < k; ++j) {
     v[0] = Tr::s_init(static_cast<const S*>(p[j])[e]);
-    tree_push<O, 1>(acc, v, tc.c[j]);
+    tree_push<Fin::kRawRoot, O, 1>(acc, v, tc.c[j], j == k - 1);
   }
-  return Tr::s_fin(v[0]);
+  return fin.s(v[0]);
 }
 
+// The nested fold in registers (round 1): f64, the 2-byte runtime-coded shapes, k outside the LDS set, and
+// the A/B reference of ftar_debug_reduce_nested_lds.  Like reduce_vec_kernel it keeps its scaled loop as a second
+// copy (reduce_tree_body below) -- a fix to one goes into both: behind a shared body all 41 plain instantiations
+// compile differently (kernarg loads hoisted to the entry), and on cold data f64 (2,3) lost 1.7 % against the
+// kernel as written here while f32 (3,3) gained 3.5 % (profiles/fold_bodies/).
 template <class Tr, int K, int U, class Sh = RuntimeShape>
 __global__ void __launch_bounds__(kThreads)
     reduce_tree_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, TreeCode tc, void* dst, size_t nvec,
@@ -851,7 +862,7 @@ __global__ void __launch_bounds__(kThreads)
 
   if (blockIdx.x == 0 && threadIdx.x < (unsigned)(head + tail)) {
     const size_t e = threadIdx.x < (unsigned)head ? threadIdx.x : (size_t)head + nvec * VE + (threadIdx.x - head);
-    static_cast<S*>(dst)[e] = tree_elem<Tr>(src.p, k, tc, e);
+    static_cast<S*>(dst)[e] = tree_elem<Tr>(src.p, k, tc, e, PlainFin<Tr>{});
   }
   auto sp = [&](int j) { return reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head); };
   u32x4* d = reinterpret_cast<u32x4*>(static_cast<S*>(dst) + head);
@@ -867,14 +878,14 @@ __global__ void __launch_bounds__(kThreads)
       for (int j = 0; j < K; ++j) {
 #pragma unroll
         for (int u = 0; u < U; ++u) v[u] = Tr::v_init(x[j][u]);
-        if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push<O, U>(acc, v, tc.c[j]);
-        else tree_push<O, U>(acc, v, Sh::code(j));
+        if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push<false, O, U>(acc, v, tc.c[j], false);
+        else tree_push<false, O, U>(acc, v, Sh::code(j), false);
       }
     } else {
       for (int j = 0; j < k; ++j) {
 #pragma unroll
         for (int u = 0; u < U; ++u) v[u] = Tr::v_init(ld16<kNtLoads>(sp(j) + v0 + u * kThreads));
-        tree_push<O, U>(acc, v, tc.c[j]);
+        tree_push<false, O, U>(acc, v, tc.c[j], false);
       }
     }
 #pragma unroll
@@ -887,83 +898,19 @@ __global__ void __launch_bounds__(kThreads)
     typename O::A acc[kTreeLevels][1], v[1];
     for (int j = 0; j < k; ++j) {
       v[0] = Tr::v_init(ld16<kNtLoads>(sp(j) + vi));
-      tree_push<O, 1>(acc, v, tc.c[j]);
+      tree_push<false, O, 1>(acc, v, tc.c[j], false);
     }
     d[vi] = Tr::v_fin(v[0]);
   }
 }
 
-template <class Tr>
-__global__ void __launch_bounds__(kThreads)
-    reduce_tree_elem_kernel(Srcs<FTAR_MAX_K> src, int k, TreeCode tc, void* dst, size_t n) {
-  using S = typename Tr::S;
-  const size_t stride = (size_t)gridDim.x * kThreads;
-  for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride)
-    static_cast<S*>(dst)[e] = tree_elem<Tr>(src.p, k, tc, e);
-}
-
-// The nested fold on the LDS-staged tile loop (lds_staged): the production
-// path for the multi-stage trees' one-round reduce-scatter up to 16 ranks.
-// Compile-time shapes (Sh = StaticShape) fold to straight-line adds; other
-// shapes read the leaf codes from the kernarg.
-template <class Tr, int K, int U, int W, class Sh>
-__global__ void __launch_bounds__(W * 64)
-    reduce_tree_lds_kernel(Srcs<K> src, TreeCode tc, void* dst, size_t nvec, int head, int tail) {
-  using O = TreeOps<Tr, true>;
-  lds_staged<Tr, K, U, W, 2, true>(
-      src, dst, nvec, head, tail,
-      [&](auto get) {
-        typename O::A acc[kTreeLevels][1], v[1];
-#pragma unroll
-        for (int j = 0; j < K; ++j) {
-          v[0] = Tr::v_init(get(j));
-          if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push<O, 1>(acc, v, tc.c[j]);
-          else tree_push<O, 1>(acc, v, Sh::code(j));
-        }
-        return Tr::v_fin(v[0]);
-      },
-      [&](size_t e) { return tree_elem<Tr>(src.p, K, tc, e); });
-}
-
-// The scaled nested fold: as tree_push, but the last leaf (`last`) leaves the root in v as its
-// level's accumulator holds it, unrounded, for the finisher to scale and round once; inner nodes are
-// rounded as ever.  The last leaf completes every level (done = L), so the root is the node that closes
-// at level done - 1.
-template <class O, int U>
-__device__ __forceinline__ void tree_push_root(typename O::A (&acc)[kTreeLevels][U], typename O::A (&v)[U],
-                                               unsigned code, bool last) {
-  const unsigned done = code & 7u;
-#pragma unroll
-  for (int l = 0; l < kTreeLevels; ++l) {
-    const bool fresh = (code >> (3 + l)) & 1u;
-#pragma unroll
-    for (int u = 0; u < U; ++u) acc[l][u] = fresh ? v[u] : O::add(acc[l][u], v[u]);
-    if (done <= (unsigned)l) break;
-    const bool root = last && done == (unsigned)l + 1;
-#pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = root ? acc[l][u] : O::rnd(acc[l][u]);
-  }
-}
-
-template <class Tr>
-__device__ __forceinline__ typename Tr::S tree_elem_scaled(const void* const* p, int k, const TreeCode& tc, size_t e,
-                                                           ScaledFin<Tr> fin) {
-  using S = typename Tr::S;
-  using O = TreeOps<Tr, false>;
-  typename O::A acc[kTreeLevels][1], v[1];
-  for (int j = 0; j < k; ++j) {
-    v[0] = Tr::s_init(static_cast<const S*>(p[j])[e]);
-    tree_push_root<O, 1>(acc, v, tc.c[j], j == k - 1);
-  }
-  return fin.s(v[0]);
-}
-
-template <class Tr, int K, int U, class Sh>
+template <class Tr, int K, int U, class Sh, class Fin>
 __device__ __forceinline__ void reduce_tree_body(const Srcs<(K > 0 ? K : FTAR_MAX_K)>& src, int kr,
                                                  const TreeCode& tc, void* dst, size_t nvec, int head, int tail,
-                                                 ScaledFin<Tr> fin) {
+                                                 Fin fin) {
   using S = typename Tr::S;
   using O = TreeOps<Tr, true>;
+  constexpr bool RAW = Fin::kRawRoot;
   const int k = K > 0 ? K : kr;
   constexpr int VE = 16 / sizeof(S);
   const size_t tile_stride = (size_t)gridDim.x * (U * kThreads);
@@ -971,7 +918,7 @@ __device__ __forceinline__ void reduce_tree_body(const Srcs<(K > 0 ? K : FTAR_MA
 
   if (blockIdx.x == 0 && threadIdx.x < (unsigned)(head + tail)) {
     const size_t e = threadIdx.x < (unsigned)head ? threadIdx.x : (size_t)head + nvec * VE + (threadIdx.x - head);
-    static_cast<S*>(dst)[e] = tree_elem_scaled<Tr>(src.p, k, tc, e, fin);
+    static_cast<S*>(dst)[e] = tree_elem<Tr>(src.p, k, tc, e, fin);
   }
   auto sp = [&](int j) { return reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head); };
   u32x4* d = reinterpret_cast<u32x4*>(static_cast<S*>(dst) + head);
@@ -987,14 +934,14 @@ __device__ __forceinline__ void reduce_tree_body(const Srcs<(K > 0 ? K : FTAR_MA
       for (int j = 0; j < K; ++j) {
 #pragma unroll
         for (int u = 0; u < U; ++u) v[u] = Tr::v_init(x[j][u]);
-        if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push_root<O, U>(acc, v, tc.c[j], j == K - 1);
-        else tree_push_root<O, U>(acc, v, Sh::code(j), j == K - 1);
+        if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push<RAW, O, U>(acc, v, tc.c[j], j == K - 1);
+        else tree_push<RAW, O, U>(acc, v, Sh::code(j), j == K - 1);
       }
     } else {
       for (int j = 0; j < k; ++j) {
 #pragma unroll
         for (int u = 0; u < U; ++u) v[u] = Tr::v_init(ld16<kNtLoads>(sp(j) + v0 + u * kThreads));
-        tree_push_root<O, U>(acc, v, tc.c[j], j == k - 1);
+        tree_push<RAW, O, U>(acc, v, tc.c[j], j == k - 1);
       }
     }
 #pragma unroll
@@ -1007,7 +954,7 @@ __device__ __forceinline__ void reduce_tree_body(const Srcs<(K > 0 ? K : FTAR_MA
     typename O::A acc[kTreeLevels][1], v[1];
     for (int j = 0; j < k; ++j) {
       v[0] = Tr::v_init(ld16<kNtLoads>(sp(j) + vi));
-      tree_push_root<O, 1>(acc, v, tc.c[j], j == k - 1);
+      tree_push<RAW, O, 1>(acc, v, tc.c[j], j == k - 1);
     }
     d[vi] = fin.v(v[0]);
   }
@@ -1019,13 +966,19 @@ __global__ void __launch_bounds__(kThreads)
   reduce_tree_body<Tr, K, U, Sh>(src, kr, tc, dst, nvec, head, tail, ScaledFin<Tr>{scale});
 }
 
-template <class Tr>
+// element-wise, for sources not co-aligned with dst
+template <class Tr, class Fin>
 __device__ __forceinline__ void reduce_tree_elem_body(const Srcs<FTAR_MAX_K>& src, int k, const TreeCode& tc,
-                                                      void* dst, size_t n, ScaledFin<Tr> fin) {
+                                                      void* dst, size_t n, Fin fin) {
   using S = typename Tr::S;
   const size_t stride = (size_t)gridDim.x * kThreads;
   for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride)
-    static_cast<S*>(dst)[e] = tree_elem_scaled<Tr>(src.p, k, tc, e, fin);
+    static_cast<S*>(dst)[e] = tree_elem<Tr>(src.p, k, tc, e, fin);
+}
+template <class Tr>
+__global__ void __launch_bounds__(kThreads)
+    reduce_tree_elem_kernel(Srcs<FTAR_MAX_K> src, int k, TreeCode tc, void* dst, size_t n) {
+  reduce_tree_elem_body<Tr>(src, k, tc, dst, n, PlainFin<Tr>{});
 }
 template <class Tr>
 __global__ void __launch_bounds__(kThreads)
@@ -1034,9 +987,13 @@ __global__ void __launch_bounds__(kThreads)
   reduce_tree_elem_body<Tr>(src, k, tc, dst, n, ScaledFin<Tr>{scale});
 }
 
-template <class Tr, int K, int U, int W, class Sh>
+// The nested fold on the LDS-staged tile loop (lds_staged): the production
+// path for the multi-stage trees' one-round reduce-scatter up to 16 ranks.
+// Compile-time shapes (Sh = StaticShape) fold to straight-line adds; other
+// shapes read the leaf codes from the kernarg.
+template <class Tr, int K, int U, int W, class Sh, class Fin>
 __device__ __forceinline__ void reduce_tree_lds_body(const Srcs<K>& src, const TreeCode& tc, void* dst, size_t nvec,
-                                                     int head, int tail, ScaledFin<Tr> fin) {
+                                                     int head, int tail, Fin fin) {
   using O = TreeOps<Tr, true>;
   lds_staged<Tr, K, U, W, 2, true>(
       src, dst, nvec, head, tail,
@@ -1045,12 +1002,17 @@ __device__ __forceinline__ void reduce_tree_lds_body(const Srcs<K>& src, const T
 #pragma unroll
         for (int j = 0; j < K; ++j) {
           v[0] = Tr::v_init(get(j));
-          if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push_root<O, 1>(acc, v, tc.c[j], j == K - 1);
-          else tree_push_root<O, 1>(acc, v, Sh::code(j), j == K - 1);
+          if constexpr (std::is_same_v<Sh, RuntimeShape>) tree_push<Fin::kRawRoot, O, 1>(acc, v, tc.c[j], j == K - 1);
+          else tree_push<Fin::kRawRoot, O, 1>(acc, v, Sh::code(j), j == K - 1);
         }
         return fin.v(v[0]);
       },
-      [&](size_t e) { return tree_elem_scaled<Tr>(src.p, K, tc, e, fin); });
+      [&](size_t e) { return tree_elem<Tr>(src.p, K, tc, e, fin); });
+}
+template <class Tr, int K, int U, int W, class Sh>
+__global__ void __launch_bounds__(W * 64)
+    reduce_tree_lds_kernel(Srcs<K> src, TreeCode tc, void* dst, size_t nvec, int head, int tail) {
+  reduce_tree_lds_body<Tr, K, U, W, Sh>(src, tc, dst, nvec, head, tail, PlainFin<Tr>{});
 }
 template <class Tr, int K, int U, int W, class Sh>
 __global__ void __launch_bounds__(W * 64)
@@ -1141,23 +1103,39 @@ __global__ void __launch_bounds__(kThreads) gather_logged_kernel(SegArgs a, int 
 // host-side launch
 // ---------------------------------------------------------------------------
 
+// How `count` elements of `esz` bytes at dst split for 16-byte access (launch_tr, launch_tree, launch_copy):
+// `head` elements up to dst's first aligned address, nvec vectors, `tail` elements (head and tail are workgroup
+// 0's, element-wise, in the same launch).  co_aligned: dst is element-aligned and every source sits at dst's
+// address mod 16; otherwise the caller takes an element-wise kernel and the rest stays 0.
+struct Split16 {
+  bool co_aligned;
+  int head = 0, tail = 0;
+  size_t nvec = 0;
+};
+inline Split16 split16(const void* const* srcs, int k, const void* dst, size_t count, size_t esz) {
+  const uintptr_t mis = reinterpret_cast<uintptr_t>(dst) & 15;
+  bool co_aligned = (mis % esz) == 0;
+  for (int j = 0; j < k && co_aligned; ++j) co_aligned = (reinterpret_cast<uintptr_t>(srcs[j]) & 15) == mis;
+  if (!co_aligned) return {false};
+  size_t head = mis ? (16 - mis) / esz : 0;
+  if (head > count) head = count;
+  const size_t nvec = (count - head) / (16 / esz);
+  return {true, (int)head, (int)(count - head - nvec * (16 / esz)), nvec};
+}
+// grid of the element-wise kernels: grid-stride beyond 8192 workgroups
+inline unsigned elem_blocks(size_t count) { return (unsigned)std::min<size_t>((count + kThreads - 1) / kThreads, 8192); }
+
 template <class Tr, int K, int U, bool NTL, bool NTS, int BS, bool SC = false>
 hipError_t launch_cfg(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
                       size_t max_blocks, double r = 1.0) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
-  Srcs<KK> a{};
-  for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
   const size_t per_block = (size_t)U * BS;
   size_t blocks = (nvec + per_block - 1) / per_block;
   if (blocks == 0) blocks = 1;  // head/tail only
   if (max_blocks && blocks > max_blocks) blocks = max_blocks;  // grid-stride over the rest
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  if constexpr (SC)
-    FTAR_LAUNCH((reduce_vec_scaled_kernel<Tr, K, U, NTL, NTS, BS>), dim3((unsigned)blocks), dim3(BS), 0, s, a, k, dst,
-                nvec, head, tail, (typename Tr::SC)r);
-  else
-    FTAR_LAUNCH((reduce_vec_kernel<Tr, K, U, NTL, NTS, BS>), dim3((unsigned)blocks), dim3(BS), 0, s, a, k, dst,
-                       nvec, head, tail);
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_vec, (Tr, K, U, NTL, NTS, BS), dim3((unsigned)blocks), dim3(BS), 0, s,
+                  pack_srcs<KK>(srcs, k), k, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
@@ -1188,17 +1166,11 @@ template <class Tr, int K, int U, class Sh = RuntimeShape, bool SC = false>
 hipError_t launch_tree_k(const void* const* srcs, int k, const TreeCode& tc, void* dst, size_t nvec, int head,
                          int tail, hipStream_t s, double r = 1.0) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
-  Srcs<KK> a{};
-  for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
   size_t blocks = (nvec + (size_t)U * kThreads - 1) / ((size_t)U * kThreads);
   if (blocks == 0) blocks = 1;
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  if constexpr (SC)
-    FTAR_LAUNCH((reduce_tree_scaled_kernel<Tr, K, U, Sh>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
-                nvec, head, tail, (typename Tr::SC)r);
-  else
-    FTAR_LAUNCH((reduce_tree_kernel<Tr, K, U, Sh>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
-                       nvec, head, tail);
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_tree, (Tr, K, U, Sh), dim3((unsigned)blocks), dim3(kThreads), 0, s,
+                  pack_srcs<KK>(srcs, k), k, tc, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
@@ -1206,16 +1178,10 @@ template <class Tr, int K, class Sh = RuntimeShape, bool SC = false>
 hipError_t launch_tree_lds(const void* const* srcs, const TreeCode& tc, void* dst, size_t nvec, int head, int tail,
                            hipStream_t s, double r = 1.0) {
   constexpr int U = kLdsTiles<Tr, K>, W = kLdsWaves<Tr, K>;
-  Srcs<K> a{};
-  for (int j = 0; j < K; ++j) a.p[j] = srcs[j];
   const size_t per_block = (size_t)W * U * 64;
   const size_t blocks = (nvec + per_block - 1) / per_block;
-  if constexpr (SC)
-    FTAR_LAUNCH((reduce_tree_lds_scaled_kernel<Tr, K, U, W, Sh>), dim3((unsigned)(blocks ? blocks : 1)),
-                dim3(W * 64), 0, s, a, tc, dst, nvec, head, tail, (typename Tr::SC)r);
-  else
-    FTAR_LAUNCH((reduce_tree_lds_kernel<Tr, K, U, W, Sh>), dim3((unsigned)(blocks ? blocks : 1)), dim3(W * 64),
-                       0, s, a, tc, dst, nvec, head, tail);
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_tree_lds, (Tr, K, U, W, Sh), dim3((unsigned)(blocks ? blocks : 1)),
+                  dim3(W * 64), 0, s, pack_srcs<K>(srcs, K), tc, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
@@ -1223,28 +1189,14 @@ template <class Tr, bool SC = false>
 hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const int* shape, int nlevels, void* dst,
                        size_t count, hipStream_t s, bool lds, double r = 1.0) {
   using S = typename Tr::S;
-  constexpr size_t VE = 16 / sizeof(S);
-  const uintptr_t mis = reinterpret_cast<uintptr_t>(dst) & 15;
-  bool co_aligned = (mis % sizeof(S)) == 0;
-  for (int j = 0; j < k && co_aligned; ++j) co_aligned = (reinterpret_cast<uintptr_t>(srcs[j]) & 15) == mis;
-  if (!co_aligned) {
-    Srcs<FTAR_MAX_K> a{};
-    for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
-    size_t blocks = (count + kThreads - 1) / kThreads;
-    blocks = blocks > 8192 ? 8192 : blocks;
-    if constexpr (SC)
-      FTAR_LAUNCH((reduce_tree_elem_scaled_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
-                  count, (typename Tr::SC)r);
-    else
-      FTAR_LAUNCH((reduce_tree_elem_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, tc, dst,
-                         count);
+  const Split16 sp = split16(srcs, k, dst, count, sizeof(S));
+  if (!sp.co_aligned) {
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_tree_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
+                    pack_srcs<FTAR_MAX_K>(srcs, k), k, tc, dst, count);
     return hipGetLastError();
   }
-  size_t head = mis ? (16 - mis) / sizeof(S) : 0;
-  if (head > count) head = count;
-  const size_t nvec = (count - head) / VE;
-  const int tail = (int)(count - head - nvec * VE);
-  const int h = (int)head;
+  const size_t nvec = sp.nvec;
+  const int h = sp.head, tail = sp.tail;
   auto is = [&](std::initializer_list<int> w) {
     return (int)w.size() == nlevels && std::equal(w.begin(), w.end(), shape);
   };
@@ -1297,39 +1249,24 @@ hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const
 // LDS kernel (tools/dtype_rates.py, profiles/r02/s4/dtype_rates*.log).
 template <class Tr, int HOT, bool SC = false>
 hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0) {
-  using S = typename Tr::S;
-  constexpr size_t VE = 16 / sizeof(S);
-  const uintptr_t mis = reinterpret_cast<uintptr_t>(dst) & 15;
-  bool co_aligned = (mis % sizeof(S)) == 0;
-  for (int j = 0; j < k && co_aligned; ++j) co_aligned = (reinterpret_cast<uintptr_t>(srcs[j]) & 15) == mis;
-  if (!co_aligned) {
-    Srcs<FTAR_MAX_K> a{};
-    for (int j = 0; j < k; ++j) a.p[j] = srcs[j];
-    size_t blocks = (count + kThreads - 1) / kThreads;
-    blocks = blocks > 8192 ? 8192 : blocks;
-    if constexpr (SC)
-      FTAR_LAUNCH((reduce_elem_scaled_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, dst, count,
-                  (typename Tr::SC)r);
-    else
-      FTAR_LAUNCH((reduce_elem_kernel<Tr>), dim3((unsigned)blocks), dim3(kThreads), 0, s, a, k, dst, count);
+  const Split16 sp = split16(srcs, k, dst, count, sizeof(typename Tr::S));
+  if (!sp.co_aligned) {
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
+                    pack_srcs<FTAR_MAX_K>(srcs, k), k, dst, count);
     return hipGetLastError();
   }
-  size_t head = mis ? (16 - mis) / sizeof(S) : 0;
-  if (head > count) head = count;
-  const size_t nvec = (count - head) / VE;
-  const size_t tail = count - head - nvec * VE;
   hipError_t e = hipErrorInvalidValue;
   bool done = false;
   [&]<int... I>(std::integer_sequence<int, I...>) {  // k = 2 .. max(2, HOT), unrolled
     ((k == I + 2 && (I + 2 == 2 || I + 2 <= HOT)
-          ? (e = launch_k<Tr, (I + 2 <= (HOT > 2 ? HOT : 2) ? I + 2 : 2), SC>(srcs, k, dst, nvec, (int)head, (int)tail,
+          ? (e = launch_k<Tr, (I + 2 <= (HOT > 2 ? HOT : 2) ? I + 2 : 2), SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail,
                                                                               s, r),
              done = true)
           : false),
      ...);
   }(std::make_integer_sequence<int, (HOT > 2 ? HOT : 2) - 1>{});
   if (done) return e;
-  return launch_k<Tr, 0, SC>(srcs, k, dst, nvec, (int)head, (int)tail, s, r);
+  return launch_k<Tr, 0, SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail, s, r);
 }
 
 }  // namespace

@@ -115,9 +115,9 @@ ftar_status_t launch_noop(hipStream_t stream) {
 
 namespace {
 // the LDS-staged kernel up to k = HOT, or (lds == false: the peer forms' ":vec" A/B) only at k = 2
-template <class Tr, int HOT>
-hipError_t tr(bool lds, const void* const* srcs, int k, void* dst, size_t count, hipStream_t s) {
-  return lds ? launch_tr<Tr, HOT>(srcs, k, dst, count, s) : launch_tr<Tr, 0>(srcs, k, dst, count, s);
+template <class Tr, int HOT, bool SC = false>
+hipError_t tr(bool lds, const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0) {
+  return lds ? launch_tr<Tr, HOT, SC>(srcs, k, dst, count, s, r) : launch_tr<Tr, 0, SC>(srcs, k, dst, count, s, r);
 }
 // MAX / MIN of one dtype; HOT as the SUM of the same element width
 template <bool MAX>
@@ -138,6 +138,41 @@ hipError_t tr_min_max(ftar_dtype_t dt, bool lds, const void* const* srcs, int k,
   }
   return hipErrorInvalidValue;
 }
+// The float sums, nested or flat, in either finish: SC = the scaled finish (AVG's root folds,
+// ftar_reduce_scaled) with the scale r.  A one-round ring fold (round_each, k > 2) of a 16-bit format rounds
+// after every add; under a scaled finish it rounds before each add instead (H16SumHopPreT), so the last sum
+// reaches the finish unrounded, as the staged ring's last hop (a plain k = 2 fold) hands it over.
+template <bool SC>
+ftar_status_t float_sum(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, hipStream_t s,
+                        bool round_each, const int* shape, int nlevels, bool lds, double r) {
+  hipError_t e = hipErrorInvalidValue;
+  const bool hop = round_each && k > 2;
+  if (nlevels > 1 && k > 1) {
+    TreeCode tc;
+    if (!shape || !make_tree_code(shape, nlevels, k, &tc)) return FTAR_ERR_INVALID_ARG;
+    switch (dt) {
+      case FTAR_FLOAT32: e = launch_tree<F32Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
+      case FTAR_FLOAT64: e = launch_tree<F64Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, false, r); break;
+      case FTAR_FLOAT16: e = launch_tree<F16Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
+      default: e = launch_tree<BF16Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
+    }
+  } else {
+    switch (dt) {
+      case FTAR_FLOAT32: e = tr<F32Sum, 16, SC>(lds, srcs, k, dst, count, s, r); break;
+      case FTAR_FLOAT64: e = tr<F64Sum, 8, SC>(lds, srcs, k, dst, count, s, r); break;
+      case FTAR_FLOAT16:
+        e = hop ? tr<std::conditional_t<SC, F16SumHopPre, F16SumHop>, 16, SC>(lds, srcs, k, dst, count, s, r)
+                : tr<F16Sum, 16, SC>(lds, srcs, k, dst, count, s, r);
+        break;
+      default:
+        e = hop ? tr<std::conditional_t<SC, BF16SumHopPre, BF16SumHop>, 16, SC>(lds, srcs, k, dst, count, s, r)
+                : tr<BF16Sum, 16, SC>(lds, srcs, k, dst, count, s, r);
+        break;
+    }
+  }
+  FTAR_CHECK_HIP(e);
+  return FTAR_SUCCESS;
+}
 }  // namespace
 
 // The LDS-staged kernel with K = 1 on one-wave workgroups of one tile (U = 1, W = 1; byte traits, so any
@@ -146,60 +181,15 @@ hipError_t tr_min_max(ftar_dtype_t dt, bool lds, const void* const* srcs, int k,
 // whose 16-byte alignments differ take the copy kernel, which handles any alignment.
 ftar_status_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t s) {
   if (!bytes || src == dst) return FTAR_SUCCESS;
-  const uintptr_t mis = reinterpret_cast<uintptr_t>(dst) & 15;
-  if ((reinterpret_cast<uintptr_t>(src) & 15) != mis) {
+  const void* srcs[1] = {src};
+  const Split16 sp = split16(srcs, 1, dst, bytes, 1);
+  if (!sp.co_aligned) {
     const Segment seg{src, dst, bytes};
     return launch_gather(&seg, 1, s);
   }
-  size_t head = mis ? 16 - mis : 0;
-  if (head > bytes) head = bytes;
-  const size_t nvec = (bytes - head) / 16;
-  const int tail = (int)(bytes - head - nvec * 16);
-  const void* srcs[1] = {src};
-  FTAR_CHECK_HIP((launch_lds<U8Sum, 1, 1, 1>(srcs, dst, nvec, s, (int)head, tail)));
+  FTAR_CHECK_HIP((launch_lds<U8Sum, 1, 1, 1>(srcs, dst, sp.nvec, s, sp.head, sp.tail)));
   return FTAR_SUCCESS;
 }
-
-namespace {
-// The scaled float sums (AVG's root folds, ftar_reduce_scaled): launch_reduce's SUM dispatch on the
-// *_scaled_kernel twins.  k = 1 is a scaled copy (the runtime-k register kernel, or the element kernel).
-// A one-round ring fold (round_each, k > 2) rounds before each add instead of after it, so the last sum
-// reaches the finisher unrounded, as the staged ring's last hop (a plain k = 2 fold) hands it over.
-template <class Tr, int HOT>
-hipError_t tr_scaled(bool lds, const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r) {
-  return lds ? launch_tr<Tr, HOT, true>(srcs, k, dst, count, s, r) : launch_tr<Tr, 0, true>(srcs, k, dst, count, s, r);
-}
-ftar_status_t launch_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, hipStream_t s,
-                            bool round_each, const int* shape, int nlevels, bool lds, double r) {
-  hipError_t e = hipErrorInvalidValue;
-  if (nlevels > 1 && k > 1) {
-    TreeCode tc;
-    if (!shape || !make_tree_code(shape, nlevels, k, &tc)) return FTAR_ERR_INVALID_ARG;
-    switch (dt) {
-      case FTAR_FLOAT32: e = launch_tree<F32Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
-      case FTAR_FLOAT64: e = launch_tree<F64Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, false, r); break;
-      case FTAR_FLOAT16: e = launch_tree<F16Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
-      default: e = launch_tree<BF16Sum, true>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
-    }
-    FTAR_CHECK_HIP(e);
-    return FTAR_SUCCESS;
-  }
-  switch (dt) {
-    case FTAR_FLOAT32: e = tr_scaled<F32Sum, 16>(lds, srcs, k, dst, count, s, r); break;
-    case FTAR_FLOAT64: e = tr_scaled<F64Sum, 8>(lds, srcs, k, dst, count, s, r); break;
-    case FTAR_FLOAT16:
-      e = round_each && k > 2 ? tr_scaled<F16SumHopPre, 16>(lds, srcs, k, dst, count, s, r)
-                              : tr_scaled<F16Sum, 16>(lds, srcs, k, dst, count, s, r);
-      break;
-    default:
-      e = round_each && k > 2 ? tr_scaled<BF16SumHopPre, 16>(lds, srcs, k, dst, count, s, r)
-                              : tr_scaled<BF16Sum, 16>(lds, srcs, k, dst, count, s, r);
-      break;
-  }
-  FTAR_CHECK_HIP(e);
-  return FTAR_SUCCESS;
-}
-}  // namespace
 
 ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
                             hipStream_t s, bool round_each, const int* shape, int nlevels, bool lds,
@@ -210,36 +200,17 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
   if (count == 0) return FTAR_SUCCESS;
   for (int j = 0; j < k; ++j)
     if (!srcs[j]) return FTAR_ERR_INVALID_ARG;
-  if (scale) return launch_scaled(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale);
+  // a scaled k = 1 is a scaled copy through the runtime-k kernel; a plain one is a copy
+  if (scale) return float_sum<true>(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale);
   if (k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)
     return launch_copy(srcs[0], dst, count * dtype_size(dt), s);
+  if (op == FTAR_SUM && dtype_scalable(dt))
+    return float_sum<false>(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, 1.0);
   hipError_t e = hipErrorInvalidValue;
-  if (nlevels > 1 && op == FTAR_SUM &&
-      (dt == FTAR_FLOAT32 || dt == FTAR_FLOAT64 || dt == FTAR_BFLOAT16 || dt == FTAR_FLOAT16)) {
-    TreeCode tc;
-    if (!shape || !make_tree_code(shape, nlevels, k, &tc)) return FTAR_ERR_INVALID_ARG;
-    switch (dt) {
-      case FTAR_FLOAT32: e = launch_tree<F32Sum>(srcs, k, tc, shape, nlevels, dst, count, s, lds); break;
-      case FTAR_FLOAT64: e = launch_tree<F64Sum>(srcs, k, tc, shape, nlevels, dst, count, s, false); break;
-      case FTAR_FLOAT16: e = launch_tree<F16Sum>(srcs, k, tc, shape, nlevels, dst, count, s, lds); break;
-      default: e = launch_tree<BF16Sum>(srcs, k, tc, shape, nlevels, dst, count, s, lds); break;
-    }
-    FTAR_CHECK_HIP(e);
-    return FTAR_SUCCESS;
-  }
   switch (op) {
   case FTAR_SUM:
     switch (dt) {
-      case FTAR_FLOAT32: e = tr<F32Sum, 16>(lds, srcs, k, dst, count, s); break;
-      case FTAR_BFLOAT16:
-        e = round_each && k > 2 ? tr<BF16SumHop, 16>(lds, srcs, k, dst, count, s)
-                                : tr<BF16Sum, 16>(lds, srcs, k, dst, count, s);
-        break;
-      case FTAR_FLOAT16:
-        e = round_each && k > 2 ? tr<F16SumHop, 16>(lds, srcs, k, dst, count, s)
-                                : tr<F16Sum, 16>(lds, srcs, k, dst, count, s);
-        break;
-      case FTAR_FLOAT64: e = tr<F64Sum, 8>(lds, srcs, k, dst, count, s); break;
+      case FTAR_FLOAT32: case FTAR_FLOAT64: case FTAR_BFLOAT16: case FTAR_FLOAT16: break;  // float_sum above
       case FTAR_UINT8: case FTAR_INT8: e = tr<U8Sum, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_UINT16: case FTAR_INT16: e = tr<U16Sum, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_INT32: e = tr<U32Sum, 8>(lds, srcs, k, dst, count, s); break;

@@ -104,6 +104,40 @@ def test_reduce_scaled_nested_unaligned_takes_the_element_kernel():
     check("f16", run_scaled(ins, "f16", 0.25, offsets=[1, 1, 1, 1], out_offset=1, shape=[2, 2]), want)
 
 
+# Each fold family is one body under two __global__ names (csrc/reduce_impl.h); profiles and tools key on the
+# names.  (call, the plain kernel's template id; the scaled one inserts "_scaled"): exact ids where the call
+# fixes every template argument, else the prefix and the shape the id must hold.
+FAMILIES = {
+    "lds": (dict(dt="f32", k=2), "reduce_lds_kernel<F32Sum, 2, 1, 2, 2, true>"),
+    "vec": (dict(dt="f32", k=17), "reduce_vec_kernel<F32Sum, 0, 2, true, true, 512>"),
+    "elem": (dict(dt="f32", k=2, offsets=[0, 1]), "reduce_elem_kernel<F32Sum>"),
+    "tree_lds": (dict(dt="f32", k=4, shape=(2, 2)), ("reduce_tree_lds_kernel<F32Sum, 4, ", "StaticShape<2, 2>")),
+    "tree": (dict(dt="f64", k=4, shape=(2, 2)), ("reduce_tree_kernel<F64Sum, 4, 2, ", "StaticShape<2, 2>")),
+    "tree_elem": (dict(dt="f32", k=4, shape=(2, 2), offsets=[0, 1, 0, 0]), "reduce_tree_elem_kernel<F32Sum>"),
+}
+
+
+@pytest.mark.parametrize("scale", [None, 0.25], ids=["plain", "scaled"])
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_every_fold_family_is_reached_under_its_name_in_both_finishes(family, scale):
+    """n = 4099: a full tile, a partial one and a tail.  The plain expectation is the same torch fold with r = 1
+    (an exact multiply)."""
+    import ftar
+    call, want_id = FAMILIES[family]
+    dt, k, shape = call["dt"], call["k"], call.get("shape")
+    ins, want = avg_ref.reduce_case(dt, k, 4099, 1.0 if scale is None else scale, shape=shape)
+    got = run_scaled(ins, dt, scale, offsets=call.get("offsets"), shape=list(shape) if shape else None)
+    name = ftar.names.kernel_symbol(ftar.last_kernel())
+    if scale is not None:
+        want_id = ([w.replace("_kernel<", "_scaled_kernel<") for w in want_id] if isinstance(want_id, tuple)
+                   else want_id.replace("_kernel<", "_scaled_kernel<"))
+    if isinstance(want_id, str):
+        assert name == want_id
+    else:
+        assert name.startswith(want_id[0]) and want_id[1] in name, (name, want_id)
+    check(dt, got, want, name)
+
+
 # ---- AllReduce on in-process groups ---------------------------------------------------------------------
 N = 50_001
 TOPOS = [(2, "1"), (3, "1"), (3, "3"), (4, "2,2"), (6, "1"), (6, "2,3"), (8, "1"), (8, "8"), (8, "2,4"),

@@ -50,7 +50,7 @@ variants = [int(v) for v in a.variants.split(",")]
 S = max(setss)
 K = max(ks)
 bufs = [[torch.rand(n, device="cuda") for _ in range(K + 1)] for _ in range(S)]  # K sources + dst per set
-ESZ = {"f32": 4, "bf16": 2, "bf16hop": 2}
+ESZ = {"f32": 4, "bf16": 2, "bf16hop": 2, "f64": 8}   # f64: nested folds only (--shapes)
 # dtype code of ftar_debug_reduce_variant for the ring's bf16 hop fold (rounds after every add; variant 62)
 CODE = {"bf16hop": ftar.DTYPE["bf16"] + 100}
 stream = torch.cuda.current_stream()
