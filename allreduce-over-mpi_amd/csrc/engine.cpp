@@ -19,31 +19,15 @@
 // is stream-ordered like any other HIP operation.
 #include <algorithm>
 #include <chrono>
-#include <condition_variable>
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
-#include <initializer_list>
-#include <cstdint>
-#include <map>
-#include <mutex>
-#include <thread>
 
 #include "engine_state.h"
 
 using ftar::hip_ignore;
 
-
 namespace ftar {
-
-namespace {
-// Host mode pieces (0 = auto): 16 MiB per block, at least split/64 (bounds the
-// number of copies for huge buckets).  4 MiB device->host copies run at only
-// ~33 GB/s; larger pieces lengthen the pipeline's fill and drain (one piece of
-// every block each).  16 MiB was the best or near-best size in every sweep
-// (profiles/r01/host/): 8 pieces per block at P = 8 x 1 GiB.
-size_t auto_host_chunk(size_t split_bytes) { return std::max<size_t>(16u << 20, split_bytes / 64); }
-}  // namespace
 
 // phase timing: one timing event per boundary, on the stream that reaches it
 ftar_status_t mark(ftar_comm* c, const std::string& name, hipStream_t s) {
@@ -69,6 +53,19 @@ ftar_status_t grow_events(ftar_comm* c, size_t n) {
     FTAR_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     c->events.push_back(e);
   }
+  return FTAR_SUCCESS;
+}
+
+ftar_status_t fork_streams(hipStream_t stream, hipEvent_t ev, std::initializer_list<hipStream_t> streams) {
+  FTAR_CHECK_HIP(hipEventRecord(ev, stream));
+  for (hipStream_t s : streams) FTAR_CHECK_HIP(hipStreamWaitEvent(s, ev, 0));
+  return FTAR_SUCCESS;
+}
+
+ftar_status_t join_streams(hipStream_t stream, std::initializer_list<Join> joins) {
+  for (const Join& j : joins)
+    if (j.record) FTAR_CHECK_HIP(hipEventRecord(j.ev, j.s));
+  for (const Join& j : joins) FTAR_CHECK_HIP(hipStreamWaitEvent(stream, j.ev, 0));
   return FTAR_SUCCESS;
 }
 
@@ -115,13 +112,24 @@ ftar_status_t set_reduce_cus(ftar_comm* c, int cus) {
   return FTAR_SUCCESS;
 }
 
-// The form the explicit settings describe (ftar_form_t), or -2 for a mix no form names.
-int form_of(const ftar_comm* c) {
-  if (c->peer_direct == FTAR_PEER_READ) return FTAR_FORM_PEER_READ;
-  if (c->peer_direct == FTAR_PEER_WRITE) return FTAR_FORM_PEER_WRITE;
-  if (c->reduce_scatter == FTAR_RS_STAGES) return c->allgather == FTAR_AG_STAGES ? FTAR_FORM_STAGES : -2;
-  if (c->allgather == FTAR_AG_DIRECT) return FTAR_FORM_DIRECT;
-  return c->allgather == FTAR_AG_COLLECTIVE ? FTAR_FORM_COLLECTIVE : -2;
+// The form a reduce-scatter, an all-gather and a peer mode make (ftar_form_t), or -2 for a mix no form names.
+int form_for(int reduce_scatter, int allgather, int peer) {
+  if (peer == FTAR_PEER_READ) return FTAR_FORM_PEER_READ;
+  if (peer == FTAR_PEER_WRITE) return FTAR_FORM_PEER_WRITE;
+  if (reduce_scatter == FTAR_RS_STAGES) return allgather == FTAR_AG_STAGES ? FTAR_FORM_STAGES : -2;
+  if (allgather == FTAR_AG_DIRECT) return FTAR_FORM_DIRECT;
+  return allgather == FTAR_AG_COLLECTIVE ? FTAR_FORM_COLLECTIVE : -2;
+}
+int form_of(const ftar_comm* c) { return form_for(c->reduce_scatter, c->allgather, c->peer_direct); }
+
+// The one decision of a call.  Host buffers on a p2p transport run staged whatever the peer mode; without p2p
+// only the peer forms move anything.
+CallPath call_path(bool host, bool p2p, int peer_mode, bool eligible, bool pipeline, bool several_pieces) {
+  if (!host && peer_mode && eligible) return CallPath::PeerDevice;
+  if (host && peer_mode == FTAR_PEER_READ && !p2p && eligible && pipeline && several_pieces)
+    return CallPath::PeerHostPipelined;
+  if (host && peer_mode && !p2p && eligible) return CallPath::PeerHostWhole;
+  return p2p ? CallPath::Staged : CallPath::Refused;
 }
 
 // "auto" | "direct" | "stages" | "collective" | "peer-read" | "peer-write"; -3 = none of them
@@ -405,22 +413,6 @@ bool comm_teardown(ftar_comm* c) {
 
 namespace {
 
-// The call's topology: the argument, or FT_TOPO/FT_LONELY read at this call; both unset: *is_auto (the
-// execution model chooses), or under FTAR_COST_MODEL=reference the reference's own model's width list.
-ftar_status_t call_topology(ftar_comm* c, const ftar_topo_t* topo, size_t bytes, Topology* t, bool* is_auto) {
-  *is_auto = false;
-  if (topo) return to_topology(topo, c->nranks, t);
-  FTAR_RETURN_IF(env_topology(c, is_auto, t));
-  const char* m = getenv("FTAR_COST_MODEL");
-  if (*is_auto && m && !strcmp(m, "reference")) {
-    ftar_topo_t ch;
-    FTAR_RETURN_IF(ftar_topo_choose(c->nranks, bytes, &ch));
-    FTAR_RETURN_IF(to_topology(&ch, c->nranks, t));
-    *is_auto = false;
-  }
-  return FTAR_SUCCESS;
-}
-
 // What the call runs: the topology, form and piece the caller fixed, the rest from the execution model
 // (cost_model.cpp), cached per communicator.  The same inputs on every rank give the same choice: the
 // model's constants are compared across ranks at the first call (agree_settings).  Peer forms are
@@ -488,6 +480,77 @@ ftar_status_t resolve_plan(ftar_comm* c, const Topology& t, size_t count, const 
   return FTAR_SUCCESS;
 }
 
+// What one call does, resolved once (resolve_call): the executor reads it, nothing is decided again.
+struct Call {
+  Topology topology;
+  ExecChoice ex;
+  Form form;
+  const Plan* plan = nullptr;
+  int peer_mode = FTAR_PEER_OFF;
+  size_t host_piece = 0;  // elements per piece of peer_allreduce_host (host buffers, no p2p), else 0
+  CallPath path = CallPath::Refused;
+};
+
+// The call's decision: call->topology holds the topology the caller or the environment fixed (topo_auto: none
+// did, the execution model chooses -- or, under FTAR_COST_MODEL=reference, the reference's own model's width
+// list); then the model's choice, the form, the plan and the path.  Writes what runs to c->last_exec
+// (ftar_comm_last_exec), also for a call that is then refused.
+ftar_status_t resolve_call(ftar_comm* c, bool topo_auto, size_t count, size_t esz, bool host, Call* call) {
+  const bool p2p = c->tp->async_p2p();
+  const char* m = getenv("FTAR_COST_MODEL");
+  if (topo_auto && m && !strcmp(m, "reference")) {
+    ftar_topo_t ch;
+    FTAR_RETURN_IF(ftar_topo_choose(c->nranks, count * esz, &ch));
+    FTAR_RETURN_IF(to_topology(&ch, c->nranks, &call->topology));
+    topo_auto = false;
+  }
+  const ExecChoice& ex = call->ex;
+  FTAR_RETURN_IF(decide_exec(c, &call->topology, topo_auto, count * esz, host, &call->ex));
+  Form& form = call->form;
+  form.allgather = c->allgather;
+  form.reduce_scatter = c->reduce_scatter;
+  call->peer_mode = c->peer_direct;
+  if (c->form == FTAR_FORM_AUTO && p2p) form_settings(ex.form, &form.allgather, &form.reduce_scatter, &call->peer_mode);
+  if (host && form.allgather == FTAR_AG_COLLECTIVE) form.allgather = FTAR_AG_DIRECT;  // D2H needs pieces
+  FTAR_RETURN_IF(resolve_plan(c, call->topology, count, form, &call->plan));
+  const Plan& plan = *call->plan;
+  call->host_piece = host && !p2p ? host_peer_piece(c, plan.split, esz) : 0;
+  call->path = call_path(host, p2p, call->peer_mode, peer_eligible(plan), c->host_peer_pipeline,
+                         call->host_piece < plan.split);
+  // what runs (ftar_comm_last_exec): a peer form exactly on the three peer paths -- rows 1-3 of call_path are
+  // "peer mode set, plan eligible, and device buffers or no p2p", each way round -- else the form of the
+  // settings' reduce-scatter and the plan's all-gather (host buffers on a p2p transport, a plan no peer kernel
+  // runs, the collective all-gather a ring or host buffers replace)
+  const bool peer = call->path == CallPath::PeerDevice || call->path == CallPath::PeerHostPipelined ||
+                    call->path == CallPath::PeerHostWhole;
+  from_topology(call->topology, &c->last_exec.topo);
+  c->last_exec.form = form_for(form.reduce_scatter, plan.allgather, peer ? call->peer_mode : FTAR_PEER_OFF);
+  // the piece: none on a whole-bucket peer path; the staged executor puts the host piece it runs
+  c->last_exec.chunk_bytes = call->path == CallPath::PeerHostPipelined ? call->host_piece * esz : peer ? 0 : ex.chunk;
+  c->last_exec.seconds = ex.seconds;
+  c->last_exec.tied = ex.tied;
+  c->last_exec.tie_broken_by = ex.tie_broken_by;
+  if (!p2p) {
+    // A host-bootstrapped communicator's paths differ in their host barriers (peer read: 3, write: 3,
+    // host buffers pipelined: m + 2, whole bucket: 3), so every rank must take the same one with the same
+    // pieces: the settings that choose it are compared first, and a mismatch fails the call on every rank
+    // (ADVICE r2) instead of pairing barriers of different phases.
+    const uint64_t cfg[6] = {(uint64_t)call->peer_mode, (uint64_t)c->allgather, (uint64_t)c->reduce_scatter,
+                             (uint64_t)host, host ? (uint64_t)c->host_peer_pipeline : 0, (uint64_t)call->host_piece};
+    bool same = true;
+    FTAR_RETURN_IF(c->tp->agree(cfg, sizeof cfg, &same));
+    if (!same) {
+      set_error("ranks disagree on the peer form, all-gather/reduce-scatter form, FTAR_HOST_PEER_PIPELINE or the "
+                "host piece size (FTAR_HOST_CHUNK_BYTES): set them alike on every rank",
+                __FILE__, __LINE__);
+      return FTAR_ERR_INVALID_ARG;
+    }
+  }
+  return FTAR_SUCCESS;
+}
+
+}  // namespace
+
 // Grow-only device buffer; before freeing the old one, drain the streams whose
 // earlier work may still touch it.
 ftar_status_t ensure_buffer(void** buf, size_t* have, size_t need, std::initializer_list<hipStream_t> users) {
@@ -504,73 +567,55 @@ ftar_status_t ensure_buffer(void** buf, size_t* have, size_t need, std::initiali
   return FTAR_SUCCESS;
 }
 
-// Per-stage dependency facts of a plan: does it move / reduce / receive into
-// scratch, the latest reducing stage before it (its data), and in the
-// stage-major order the last reader of the scratch half it receives into.
-struct StageFacts {
-  std::vector<char> moves, reduces, to_scratch;
-  std::vector<long> prev_red, war;
-  explicit StageFacts(const Plan& plan) {
-    const size_t nst = plan.stages.size();
-    moves.assign(nst, 0);
-    reduces.assign(nst, 0);
-    to_scratch.assign(nst, 0);
-    prev_red.assign(nst, -1);
-    war.assign(nst, -1);
-    long last = -1, owner[2] = {-1, -1};
-    for (size_t s = 0; s < nst; ++s) {
-      const Stage& st = plan.stages[s];
-      moves[s] = !st.sends.empty() || !st.recvs.empty();
-      reduces[s] = !st.reduces.empty();
-      for (const Transfer& x : st.recvs) to_scratch[s] |= x.buf == BUF_SCRATCH;
-      prev_red[s] = last;
-      war[s] = to_scratch[s] ? owner[s % 2] : -1;
-      if (reduces[s]) {
-        last = (long)s;
-        if (to_scratch[s]) owner[s % 2] = (long)s;
-      }
-    }
-  }
-};
-
-// Skewed execution gives every stage its own scratch region: delta[s] moves a
-// stage's scratch offsets from its alternating half to that region.  Returns
-// the scratch elements needed.
-size_t per_stage_scratch(const Plan& plan, std::vector<long>* delta) {
-  const size_t nst = plan.stages.size();
-  delta->assign(nst, 0);
-  size_t base = 0;
-  for (size_t s = 0; s < nst; ++s) {
-    const size_t half_base = (s % 2) * plan.scratch_half;
-    size_t used = 0;
-    for (const Transfer& x : plan.stages[s].recvs)
-      if (x.buf == BUF_SCRATCH) used = std::max(used, x.off - half_base + x.len);
-    (*delta)[s] = (long)base - (long)half_base;
-    base += used;
-  }
-  return base;
-}
-
-// Order of the (stage, piece) steps, identical on every rank.  Stage-major, or
-// skewed: stage s+1 trails stage s by one piece.
-std::vector<std::pair<size_t, size_t>> step_order(size_t nst, size_t nchunks, bool skew) {
-  std::vector<std::pair<size_t, size_t>> order;
-  order.reserve(nst * nchunks);
-  if (!skew) {
-    for (size_t s = 0; s < nst; ++s)
-      for (size_t k = 0; k < nchunks; ++k) order.emplace_back(s, k);
-  } else {
-    for (size_t tt = 0; tt < nchunks + nst - 1; ++tt)
-      for (size_t s = 0; s < nst && s <= tt; ++s)
-        if (tt - s < nchunks) order.emplace_back(s, tt - s);
-  }
-  return order;
-}
-
-}  // namespace
-
+// What one call runs, under the communicator's lock (allreduce): the early exits in the reference's order,
+// one decision (resolve_call), one executor.
 ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                               const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host);
+                               const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host) {
+  const size_t esz = dtype_size(dt);
+  if (sendbuf == recvbuf) sendbuf = nullptr;
+  // The call's topology: the argument, or FT_TOPO/FT_LONELY read at this call; both unset: topo_auto.  It is
+  // checked first, as get_stages runs before the P <= 1 copy (mpi_mod.hpp:1732-1746)
+  Call call;
+  bool topo_auto = false;
+  FTAR_RETURN_IF(topo ? to_topology(topo, c->nranks, &call.topology) : env_topology(c, &topo_auto, &call.topology));
+  if (c->broken) return first_contact(c);  // reports why
+  if (!c->settings_agreed && !c->capturing) {  // an RCCL communicator's first call (see comm_setup); a
+    FTAR_RETURN_IF(first_contact(c));          // 1-rank one too, which exercises the same all-gather
+    c->settings_agreed = true;
+  }
+  if (c->nranks == 1) {  // mpi_mod.hpp:1739-1746
+    if (sendbuf && count && host)
+      FTAR_CHECK_HIP(hipMemcpyAsync(recvbuf, sendbuf, count * esz, hipMemcpyHostToHost, stream));
+    if (sendbuf && count && !host) return launch_copy(sendbuf, recvbuf, count * esz, stream);
+    return FTAR_SUCCESS;
+  }
+  if (count == 0) return FTAR_SUCCESS;
+
+  FTAR_RETURN_IF(resolve_call(c, topo_auto, count, esz, host != nullptr, &call));
+  const Plan& plan = *call.plan;
+  switch (call.path) {
+    case CallPath::PeerDevice:
+      FTAR_RETURN_IF(grow_events(c, 5));
+      return peer_allreduce(sendbuf, recvbuf, count, dt, op, plan, c, stream, call.peer_mode);
+    case CallPath::PeerHostPipelined:
+      // host buffers on a transport without p2p (a communicator bootstrapped over MPI with no RCCL,
+      // ftar_comm_init_host): the read form piece by piece, H2D / exchange / D2H overlapped.  A bucket
+      // of one piece per block gains nothing from it and takes the whole-bucket path, whose one
+      // copy each way beats one per block (C1 through the MPI harness: 0.453 vs 0.487 ms)
+      FTAR_RETURN_IF(grow_events(c, 5));
+      return peer_allreduce_host(*host, count, dt, op, plan, c, stream, call.host_piece);
+    case CallPath::PeerHostWhole:  // the write form (or FTAR_HOST_PEER_PIPELINE=0)
+      return peer_allreduce_host_whole(*host, count, dt, op, plan, c, stream, call.peer_mode);
+    case CallPath::Refused:  // a transport without p2p (ftar_comm_init_host): refused before anything moves
+      set_error("this communicator has no point-to-point transfers: one-round plans in the peer-direct forms only "
+                "(ftar_comm_set_peer_direct; staged forms and lonely ranks need RCCL)",
+                __FILE__, __LINE__);
+      return FTAR_ERR_UNSUPPORTED;
+    case CallPath::Staged:
+      break;
+  }
+  return staged_allreduce(sendbuf, recvbuf, count, dt, op, plan, call.ex.chunk, c, stream, host);
+}
 
 // One call on a communicator.  Calls share the communicator's scratch, staging
 // and exchange buffers; the internal streams join the caller's stream at entry,
@@ -633,292 +678,6 @@ ftar_status_t allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_d
     c->done_recorded = true;
   }
   return st;
-}
-
-ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                               const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host) {
-  const size_t esz = dtype_size(dt);
-  if (sendbuf == recvbuf) sendbuf = nullptr;
-  {  // the topology is checked first, as get_stages runs before the P <= 1 copy (mpi_mod.hpp:1732-1746)
-    Topology t;
-    bool is_auto = false;
-    FTAR_RETURN_IF(topo ? to_topology(topo, c->nranks, &t) : env_topology(c, &is_auto, &t));
-  }
-  if (c->broken) return first_contact(c);  // reports why
-  if (!c->settings_agreed && !c->capturing) {  // an RCCL communicator's first call (see comm_setup); a
-    FTAR_RETURN_IF(first_contact(c));          // 1-rank one too, which exercises the same all-gather
-    c->settings_agreed = true;
-  }
-  if (c->nranks == 1) {  // mpi_mod.hpp:1739-1746
-    if (sendbuf && count && host)
-      FTAR_CHECK_HIP(hipMemcpyAsync(recvbuf, sendbuf, count * esz, hipMemcpyHostToHost, stream));
-    if (sendbuf && count && !host) return launch_copy(sendbuf, recvbuf, count * esz, stream);
-    return FTAR_SUCCESS;
-  }
-  if (count == 0) return FTAR_SUCCESS;
-
-  Topology topology;
-  bool topo_auto = false;
-  FTAR_RETURN_IF(call_topology(c, topo, count * esz, &topology, &topo_auto));
-  ExecChoice ex;
-  FTAR_RETURN_IF(decide_exec(c, &topology, topo_auto, count * esz, host != nullptr, &ex));
-  Form form;
-  form.allgather = c->allgather;
-  form.reduce_scatter = c->reduce_scatter;
-  int peer_mode = c->peer_direct;
-  if (c->form == FTAR_FORM_AUTO && c->tp->async_p2p())
-    form_settings(ex.form, &form.allgather, &form.reduce_scatter, &peer_mode);
-  if (host && form.allgather == FTAR_AG_COLLECTIVE) form.allgather = FTAR_AG_DIRECT;  // D2H needs pieces
-  const Plan* planp = nullptr;
-  FTAR_RETURN_IF(resolve_plan(c, topology, count, form, &planp));
-  const Plan& plan = *planp;
-  const FoldOp fo = fold_op(op, dt, c->nranks);  // AVG: SUM, scaled by 1 / P on the plan's root items
-  // what runs (ftar_comm_last_exec): the model's or the settings' form, unless the plan or the buffers send
-  // the call down another path below (host buffers on a p2p transport, a plan no peer kernel runs, the
-  // collective all-gather a ring or host buffers replace)
-  const bool peer_path = peer_mode && peer_eligible(plan) && (!host || !c->tp->async_p2p());
-  int ran = ex.form;
-  if (peer_path) ran = peer_mode == FTAR_PEER_READ ? FTAR_FORM_PEER_READ : FTAR_FORM_PEER_WRITE;
-  else if (form.reduce_scatter == FTAR_RS_STAGES) ran = plan.allgather == FTAR_AG_STAGES ? FTAR_FORM_STAGES : -2;
-  else ran = plan.allgather == FTAR_AG_DIRECT ? FTAR_FORM_DIRECT
-             : plan.allgather == FTAR_AG_COLLECTIVE ? FTAR_FORM_COLLECTIVE : -2;
-  from_topology(topology, &c->last_exec.topo);
-  c->last_exec.form = ran;
-  c->last_exec.chunk_bytes = peer_path ? 0 : ex.chunk;  // the host paths below put the piece they run
-  c->last_exec.seconds = ex.seconds;
-  c->last_exec.tied = ex.tied;
-  c->last_exec.tie_broken_by = ex.tie_broken_by;
-  const size_t nst = plan.stages.size();
-  if (!c->tp->async_p2p()) {
-    // A host-bootstrapped communicator's paths differ in their host barriers (peer read: 3, write: 3,
-    // host buffers pipelined: m + 2, whole bucket: 3), so every rank must take the same one with the same
-    // pieces: the settings that choose it are compared first, and a mismatch fails the call on every rank
-    // (ADVICE r2) instead of pairing barriers of different phases.
-    const uint64_t cfg[6] = {(uint64_t)peer_mode, (uint64_t)c->allgather, (uint64_t)c->reduce_scatter,
-                             (uint64_t)(host != nullptr), host ? (uint64_t)c->host_peer_pipeline : 0,
-                             host ? (uint64_t)host_peer_piece(c, plan.split, esz) : 0};
-    bool same = true;
-    FTAR_RETURN_IF(c->tp->agree(cfg, sizeof cfg, &same));
-    if (!same) {
-      set_error("ranks disagree on the peer form, all-gather/reduce-scatter form, FTAR_HOST_PEER_PIPELINE or the "
-                "host piece size (FTAR_HOST_CHUNK_BYTES): set them alike on every rank",
-                __FILE__, __LINE__);
-      return FTAR_ERR_INVALID_ARG;
-    }
-  }
-  if (!host && peer_mode && peer_eligible(plan)) {
-    FTAR_RETURN_IF(grow_events(c, 5));
-    return peer_allreduce(sendbuf, recvbuf, count, dt, op, plan, c, stream, peer_mode);
-  }
-  if (host && peer_mode == FTAR_PEER_READ && !c->tp->async_p2p() && peer_eligible(plan) &&
-      c->host_peer_pipeline && host_peer_piece(c, plan.split, esz) < plan.split) {
-    // host buffers on a transport without p2p (a communicator bootstrapped over MPI with no RCCL,
-    // ftar_comm_init_host): the read form piece by piece, H2D / exchange / D2H overlapped.  A bucket
-    // of one piece per block gains nothing from it and takes the whole-bucket path below, whose one
-    // copy each way beats one per block (C1 through the MPI harness: 0.453 vs 0.487 ms)
-    FTAR_RETURN_IF(grow_events(c, 5));
-    c->last_exec.chunk_bytes = host_peer_piece(c, plan.split, esz) * esz;
-    return peer_allreduce_host(*host, count, dt, op, plan, c, stream);
-  }
-  if (host && peer_mode && !c->tp->async_p2p() && peer_eligible(plan)) {
-    // the write form (or FTAR_HOST_PEER_PIPELINE=0): the whole bucket in, the peer exchange in HBM,
-    // the whole bucket out -- same plan, same bits, not pipelined (transports with stream-ordered
-    // p2p keep using the pipelined p2p path below for host buffers even in peer-direct mode)
-    const size_t bytes = count * esz;
-    if (bytes > c->staging_bytes) FTAR_RETURN_IF(refuse_growth_under_capture(c, "the staging buffer"));
-    FTAR_RETURN_IF(ensure_buffer(&c->staging, &c->staging_bytes, bytes, {c->h2d_s, c->comm_s, c->red_s, c->d2h_s}));
-    FTAR_CHECK_HIP(hipMemcpyAsync(c->staging, host->src, bytes, hipMemcpyHostToDevice, stream));
-    FTAR_RETURN_IF(grow_events(c, 5));
-    FTAR_RETURN_IF(peer_allreduce(nullptr, c->staging, count, dt, op, plan, c, stream, peer_mode));
-    FTAR_CHECK_HIP(hipMemcpyAsync(host->dst, c->staging, bytes, hipMemcpyDeviceToHost, stream));
-    return FTAR_SUCCESS;
-  }
-
-  if (!c->tp->async_p2p()) {  // a transport without p2p (ftar_comm_init_host): refused before anything moves
-    set_error("this communicator has no point-to-point transfers: one-round plans in the peer-direct forms only "
-              "(ftar_comm_set_peer_direct; staged forms and lonely ranks need RCCL)",
-              __FILE__, __LINE__);
-    return FTAR_ERR_UNSUPPORTED;
-  }
-
-  // Host mode: the buffers are in host memory and move through a device
-  // staging buffer, piece by piece, so H2D (PCIe in), the exchange, and D2H
-  // (PCIe out) run at the same time.  Every src/dst transfer and reduce of a
-  // plan covers whole blocks from their start (tests/test_plan.py), so piece
-  // k of every stage touches exactly piece k of each block: the same bytes,
-  // the same partition, the same bits as the device path.
-  // the piece: fixed, or the model's (0 = whole blocks)
-  size_t chunk_bytes = c->chunk_bytes ? c->chunk_bytes : ex.chunk ? ex.chunk : plan.split * esz;
-  if (host) {
-    chunk_bytes = c->host_chunk_bytes ? c->host_chunk_bytes : auto_host_chunk(plan.split * esz);
-    c->last_exec.chunk_bytes = std::max<size_t>(64, (chunk_bytes / esz) & ~size_t(63)) * esz;  // the piece run
-    if (count * esz > c->staging_bytes) FTAR_RETURN_IF(refuse_growth_under_capture(c, "the staging buffer"));
-    FTAR_RETURN_IF(ensure_buffer(&c->staging, &c->staging_bytes, count * esz, {c->h2d_s, c->comm_s, c->red_s, c->d2h_s}));
-    sendbuf = nullptr;
-    recvbuf = c->staging;
-  }
-  const size_t chunk = std::max<size_t>(64, (chunk_bytes / esz) & ~size_t(63));
-  const size_t nchunks = std::max<size_t>(1, (plan.split + chunk - 1) / chunk);
-  const StageFacts f(plan);
-  const std::vector<char>& moves = f.moves;
-  const std::vector<char>& reduces = f.reduces;
-  const std::vector<long>& prev_red = f.prev_red;
-  const std::vector<long>& war = f.war;
-  // Device: stage-major.  Host: skewed, so the all-gather of piece k (and its
-  // D2H) runs while later pieces are still coming in over PCIe; skewed steps
-  // of stages two apart may overlap in time, so every stage gets its own
-  // scratch region instead of alternating halves.
-  const bool skew = host != nullptr;
-  std::vector<long> delta(nst, 0);
-  const size_t scratch_elems = skew ? per_stage_scratch(plan, &delta) : 2 * plan.scratch_half;
-  if (scratch_elems * esz > c->scratch_bytes) {
-    FTAR_RETURN_IF(refuse_growth_under_capture(c, "the scratch buffer"));
-    if (c->scratch_rccl) {  // the old scratch is about to be freed: drop its RCCL registration first
-      FTAR_CHECK_HIP(hipStreamSynchronize(c->comm_s));
-      FTAR_CHECK_HIP(hipStreamSynchronize(c->red_s));
-      c->tp->rccl_deregister(c->scratch_rccl);
-      c->scratch_rccl = nullptr;
-    }
-  }
-  FTAR_RETURN_IF(ensure_buffer(&c->scratch, &c->scratch_bytes, scratch_elems * esz, {c->comm_s, c->red_s}));
-  if (c->rccl_reg && !c->scratch_rccl && c->scratch && !c->capturing)
-    c->scratch_rccl = c->tp->rccl_register(c->scratch, c->scratch_bytes);
-  const std::vector<std::pair<size_t, size_t>> order = step_order(nst, nchunks, skew);
-
-  FTAR_RETURN_IF(grow_events(c, 2 * nst * nchunks + 2 * nchunks + 5));
-  hipEvent_t* ev = c->events.data();
-  auto ev_x = [&](size_t s, size_t k) { return ev[5 + (s * nchunks + k) * 2]; };
-  auto ev_r = [&](size_t s, size_t k) { return ev[5 + (s * nchunks + k) * 2 + 1]; };
-  auto ev_h = [&](size_t k) { return ev[5 + 2 * nst * nchunks + 2 * k]; };
-  auto ev_d = [&](size_t k) { return ev[5 + 2 * nst * nchunks + 2 * k + 1]; };
-
-  char* bufs[3] = {static_cast<char*>(const_cast<void*>(sendbuf ? sendbuf : recvbuf)), static_cast<char*>(recvbuf),
-                   static_cast<char*>(c->scratch)};
-  Transport* tp = c->tp.get();
-  const size_t P = (size_t)c->nranks, split = plan.split;
-  // piece k of every block: [b*split + k*chunk, ...) clipped to the block and to count
-  auto for_piece = [&](size_t k, auto&& fn) -> ftar_status_t {
-    for (size_t b = 0; b < P; ++b) {
-      const size_t lo = b * split + k * chunk, end = std::min(count, (b + 1) * split);
-      if (lo < end) FTAR_RETURN_IF(fn(lo, std::min(chunk, end - lo)));
-    }
-    return FTAR_SUCCESS;
-  };
-
-  FTAR_CHECK_HIP(hipEventRecord(ev[0], stream));
-  FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, ev[0], 0));
-  FTAR_CHECK_HIP(hipStreamWaitEvent(c->red_s, ev[0], 0));
-  c->nmarks = 0;
-  FTAR_RETURN_IF(mark(c, "start", c->comm_s));
-  // Host mode: the pieces go in, in order, on their own stream, issued kHostLookahead pieces ahead of the
-  // steps that read them rather than all up front.  The copy stream then runs ahead of the exchange by
-  // that many pieces either way, and a stream that shares its hardware queue with it (8 streams of two
-  // in-process ranks on HIP's 4 queues, or a caller's own streams) waits behind those few pieces, not
-  // behind the whole bucket: with every piece issued first, two ranks on one GPU started the exchange only
-  // once the last piece was in, and H2D and D2H never overlapped (profiles/r05/host_local/).
-  size_t h2d_issued = 0;
-  auto issue_h2d = [&](size_t upto) -> ftar_status_t {  // pieces [h2d_issued, upto] of every block
-    for (; h2d_issued <= upto && h2d_issued < nchunks; ++h2d_issued) {
-      const size_t k = h2d_issued;
-      FTAR_RETURN_IF(for_piece(k, [&](size_t lo, size_t n) -> ftar_status_t {
-        FTAR_CHECK_HIP(hipMemcpyAsync(bufs[BUF_DST] + lo * esz, host->src + lo * esz, n * esz,
-                                      hipMemcpyHostToDevice, c->h2d_s));
-        return FTAR_SUCCESS;
-      }));
-      FTAR_CHECK_HIP(hipEventRecord(ev_h(k), c->h2d_s));
-    }
-    return FTAR_SUCCESS;
-  };
-  if (host) {
-    FTAR_CHECK_HIP(hipStreamWaitEvent(c->h2d_s, ev[0], 0));
-    FTAR_CHECK_HIP(hipStreamWaitEvent(c->d2h_s, ev[0], 0));
-    FTAR_RETURN_IF(issue_h2d(kHostLookahead));
-  }
-  std::vector<char> comm_has_input(host ? nchunks : 0), red_has_input(host ? nchunks : 0);
-  std::vector<const void*> srcs;
-  auto sbuf = [&](int buf, size_t off, size_t s) -> char* {
-    return bufs[buf] + (buf == BUF_SCRATCH ? (size_t)((long)off + delta[s]) : off) * esz;
-  };
-  for (const auto& step : order) {
-    const size_t s = step.first, k = step.second, lo = k * chunk;
-    const Stage& st = plan.stages[s];
-    if (host) FTAR_RETURN_IF(issue_h2d(k + kHostLookahead));
-    if (moves[s]) {
-      if (host && !comm_has_input[k]) {
-        FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, ev_h(k), 0));
-        comm_has_input[k] = 1;
-      }
-      // WAR on the scratch half this stage receives into (stage-major only):
-      // every reduce that read it (stage s-2, or earlier when stages in between
-      // were empty) must be done.  When stage s-1 reduced, its piece-0 event
-      // already implies this (the reduce stream runs in order), so the wait is
-      // free; it matters when s-1 was empty.
-      if (!skew && k == 0 && war[s] >= 0)
-        FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, ev_r((size_t)war[s], nchunks - 1), 0));
-      if (prev_red[s] >= 0) FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, ev_r((size_t)prev_red[s], k), 0));
-      FTAR_RETURN_IF(tp->group_start());
-      for (const Transfer& x : st.sends)
-        if (x.len > lo)
-          FTAR_RETURN_IF(tp->send(sbuf(x.buf, x.off + lo, s), std::min(chunk, x.len - lo) * esz, x.peer, c->comm_s));
-      for (const Transfer& x : st.recvs)
-        if (x.len > lo)
-          FTAR_RETURN_IF(tp->recv(sbuf(x.buf, x.off + lo, s), std::min(chunk, x.len - lo) * esz, x.peer, c->comm_s));
-      FTAR_RETURN_IF(tp->group_end());
-    }
-    if (reduces[s]) {
-      FTAR_CHECK_HIP(hipEventRecord(ev_x(s, k), c->comm_s));
-      FTAR_CHECK_HIP(hipStreamWaitEvent(c->red_s, ev_x(s, k), 0));
-      if (host && !red_has_input[k]) {
-        FTAR_CHECK_HIP(hipStreamWaitEvent(c->red_s, ev_h(k), 0));
-        red_has_input[k] = 1;
-      }
-      for (const ReduceItem& r : st.reduces) {
-        if (r.len <= lo) continue;
-        srcs.clear();
-        for (const Operand& o : r.srcs) srcs.push_back(sbuf(o.buf, o.off + lo, s));
-        FTAR_RETURN_IF(launch_reduce(srcs.data(), (int)srcs.size(), bufs[BUF_DST] + (r.off + lo) * esz,
-                                     std::min(chunk, r.len - lo), dt, fo.op, c->red_s, r.round_each, r.shape.data(),
-                                     (int)r.shape.size(), true, fo.scale(r.root)));
-      }
-      FTAR_CHECK_HIP(hipEventRecord(ev_r(s, k), c->red_s));
-    }
-    if (c->phase_timing && !skew && k == nchunks - 1) {  // stage-major: the stage's last piece
-      if (moves[s]) FTAR_RETURN_IF(mark(c, "stage " + std::to_string(s) + " moved", c->comm_s));
-      if (reduces[s]) FTAR_RETURN_IF(mark(c, "stage " + std::to_string(s) + " reduced", c->red_s));
-    }
-    if (host && s == nst - 1) {  // piece k is final everywhere: out over PCIe while later pieces come in
-      FTAR_CHECK_HIP(hipEventRecord(ev_d(k), reduces[s] ? c->red_s : c->comm_s));
-      if (reduces[s]) FTAR_CHECK_HIP(hipStreamWaitEvent(c->d2h_s, ev_x(s, k), 0));
-      else if (prev_red[s] >= 0)  // a rank idle in the last stage: its block's final fold
-        FTAR_CHECK_HIP(hipStreamWaitEvent(c->d2h_s, ev_r((size_t)prev_red[s], k), 0));
-      FTAR_CHECK_HIP(hipStreamWaitEvent(c->d2h_s, ev_d(k), 0));
-      FTAR_RETURN_IF(for_piece(k, [&](size_t lo2, size_t n) -> ftar_status_t {
-        FTAR_CHECK_HIP(hipMemcpyAsync(host->dst + lo2 * esz, bufs[BUF_DST] + lo2 * esz, n * esz,
-                                      hipMemcpyDeviceToHost, c->d2h_s));
-        return FTAR_SUCCESS;
-      }));
-    }
-  }
-  if (host) FTAR_RETURN_IF(issue_h2d(nchunks - 1));  // (every piece is read by a step; kept for safety)
-  if (plan.allgather == FTAR_AG_COLLECTIVE) {  // the whole all-gather phase as one collective, in place
-    const long last_red = nst ? (reduces[nst - 1] ? (long)nst - 1 : prev_red[nst - 1]) : -1;
-    if (last_red >= 0) FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, ev_r((size_t)last_red, nchunks - 1), 0));
-    FTAR_RETURN_IF(tp->allgather(bufs[BUF_DST] + (size_t)c->rank * plan.split * esz, bufs[BUF_DST], plan.split * esz,
-                                 c->rank, c->nranks, c->comm_s));
-  }
-  if (plan.allgather == FTAR_AG_COLLECTIVE) FTAR_RETURN_IF(mark(c, "collective all-gather", c->comm_s));
-  FTAR_RETURN_IF(tp->before_join());
-  FTAR_CHECK_HIP(hipEventRecord(ev[1], c->comm_s));
-  FTAR_CHECK_HIP(hipEventRecord(ev[2], c->red_s));
-  FTAR_CHECK_HIP(hipStreamWaitEvent(stream, ev[1], 0));
-  FTAR_CHECK_HIP(hipStreamWaitEvent(stream, ev[2], 0));
-  if (host) {
-    FTAR_CHECK_HIP(hipEventRecord(ev[3], c->h2d_s));
-    FTAR_CHECK_HIP(hipEventRecord(ev[4], c->d2h_s));
-    FTAR_CHECK_HIP(hipStreamWaitEvent(stream, ev[3], 0));
-    FTAR_CHECK_HIP(hipStreamWaitEvent(stream, ev[4], 0));
-  }
-  return FTAR_SUCCESS;
 }
 
 }  // namespace ftar

@@ -239,6 +239,11 @@ ftar_status_t ftar_comm_set_peer_direct(ftar_comm_t comm, int mode) {
   return FTAR_SUCCESS;
 }
 
+// Test hook (not in ftar.h): the path a call takes (ftar::CallPath as an int) for the six facts that decide it.
+int ftar_debug_call_path(int host, int p2p, int peer_mode, int eligible, int pipeline, int several_pieces) {
+  return (int)ftar::call_path(host != 0, p2p != 0, peer_mode, eligible != 0, pipeline != 0, several_pieces != 0);
+}
+
 // Test/tuning hook (not in ftar.h): peer-form copies nontemporal (nt) or not,
 // fold through the LDS-staged kernel (lds) or the register kernel.
 ftar_status_t ftar_debug_set_peer_tuning(ftar_comm_t comm, int nt, int lds) {

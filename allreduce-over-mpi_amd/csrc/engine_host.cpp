@@ -1,6 +1,6 @@
 // Host buffers on a host-bootstrapped communicator (engine_state.h): the read form piece by piece, H2D /
-// exchange / D2H overlapped (the MPI drop-in's `ipc` transport).  Split out of engine.cpp (round 5); no
-// behaviour change.
+// exchange / D2H overlapped (the MPI drop-in's `ipc` transport), and either form on the whole bucket.
+// Split out of engine.cpp (round 5); no behaviour change.
 #include <algorithm>
 #include <cstring>
 
@@ -82,7 +82,7 @@ static ftar_status_t log_gather(ftar_comm* c, const std::vector<Segment>& segs, 
 // fold of that piece), so pieces never conflict.  The barriers synchronise the host: m pieces take
 // m + 2 barriers, the last so that no peer still reads my X when the next call's H2D refills it.
 ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t dt, ftar_op_t op, const Plan& plan,
-                                  ftar_comm* c, hipStream_t stream) {
+                                  ftar_comm* c, hipStream_t stream, size_t chunk) {
   const size_t esz = dtype_size(dt), bytes = count * esz;
   FTAR_RETURN_IF(ensure_xbuf(c, bytes));  // collective, before the first barrier
   Transport* tp = c->tp.get();
@@ -91,7 +91,6 @@ ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t d
   const Stage& rs = plan.stages[0];
   const Stage& ag = plan.stages[1];
   const size_t P = (size_t)c->nranks, split = plan.split;
-  const size_t chunk = host_peer_piece(c, split, esz);
   const size_t m = std::max<size_t>(1, (split + chunk - 1) / chunk);
   // The D2H pieces go on the reduce stream, which this path leaves idle (its folds and gathers run on
   // the comm stream): on 4 hardware queues the H2D and D2H streams of a host-bootstrapped communicator
@@ -122,13 +121,6 @@ ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t d
   hipEvent_t* ev = c->events.data();
   auto ev_h = [&](size_t k) { return c->events[5 + 2 * k]; };      // piece k is in my X
   auto ev_g = [&](size_t k) { return c->events[5 + 2 * k + 1]; };  // piece k is final in my X
-  auto for_piece = [&](size_t k, auto&& fn) -> ftar_status_t {  // piece k of every block, clipped
-    for (size_t b = 0; b < P; ++b) {
-      const size_t lo = b * split + k * chunk, end = std::min(count, (b + 1) * split);
-      if (lo < end) FTAR_RETURN_IF(fn(lo, std::min(chunk, end - lo)));
-    }
-    return FTAR_SUCCESS;
-  };
   // Order matters when the copy streams share a hardware queue with the comm stream (HIP's 4 queues
   // per process): commands of a shared queue run in issue order, and a barrier waits for the
   // comm stream.  So every H2D piece is issued after the fold commands of an earlier piece (never all
@@ -138,7 +130,7 @@ ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t d
   auto issue_h2d = [&](size_t upto) -> ftar_status_t {  // pieces [h2d_issued, upto]
     for (; h2d_issued <= upto && h2d_issued < m; ++h2d_issued) {
       const size_t k = h2d_issued;
-      FTAR_RETURN_IF(for_piece(k, [&](size_t lo, size_t n) -> ftar_status_t {
+      FTAR_RETURN_IF(for_piece(P, split, chunk, count, k, [&](size_t lo, size_t n) -> ftar_status_t {
         FTAR_CHECK_HIP(hipMemcpyAsync(X + lo * esz, io.src + lo * esz, n * esz, hipMemcpyHostToDevice, c->h2d_s));
         return FTAR_SUCCESS;
       }));
@@ -150,7 +142,7 @@ ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t d
   auto issue_d2h = [&](size_t k) -> ftar_status_t {  // piece k of the whole bucket, once it is final here
     FTAR_CHECK_HIP(hipStreamWaitEvent(d2h, ev_g(k), 0));
     FTAR_RETURN_IF(mark(c, "d2h " + std::to_string(k) + " start", d2h));
-    FTAR_RETURN_IF(for_piece(k, [&](size_t lo2, size_t n) -> ftar_status_t {
+    FTAR_RETURN_IF(for_piece(P, split, chunk, count, k, [&](size_t lo2, size_t n) -> ftar_status_t {
       FTAR_CHECK_HIP(hipMemcpyAsync(io.dst + lo2 * esz, X + lo2 * esz, n * esz, hipMemcpyDeviceToHost, d2h));
       return FTAR_SUCCESS;
     }));
@@ -181,8 +173,7 @@ ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t d
   };
   work([&]() -> ftar_status_t {
     ev = c->events.data();
-    FTAR_CHECK_HIP(hipEventRecord(ev[0], stream));
-    for (hipStream_t s : {c->comm_s, c->h2d_s, d2h}) FTAR_CHECK_HIP(hipStreamWaitEvent(s, ev[0], 0));
+    FTAR_RETURN_IF(fork_streams(stream, ev[0], {c->comm_s, c->h2d_s, d2h}));
     c->nmarks = 0;
     FTAR_RETURN_IF(mark(c, "start", c->comm_s));
     FTAR_RETURN_IF(issue_h2d(lookahead));
@@ -254,9 +245,22 @@ ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t d
   if (st != FTAR_SUCCESS) return leave();
   FTAR_RETURN_IF(mark(c, "barrier", c->comm_s));
   FTAR_RETURN_IF(tp->before_join());
-  FTAR_CHECK_HIP(hipEventRecord(ev[1], c->comm_s));
-  FTAR_CHECK_HIP(hipEventRecord(ev[3], c->h2d_s));
-  for (int i = 1; i <= 3; ++i) FTAR_CHECK_HIP(hipStreamWaitEvent(stream, ev[i], 0));
+  return join_streams(stream, {{ev[1], c->comm_s}, {ev[2], d2h, false}, {ev[3], c->h2d_s}});  // ev[2]: on d2h, above
+}
+
+// Host buffers on a communicator without point-to-point transfers, the write form (or
+// FTAR_HOST_PEER_PIPELINE=0, or a bucket of one piece per block): the whole bucket in, the peer exchange in
+// HBM, the whole bucket out -- same plan, same bits, not pipelined (transports with stream-ordered p2p
+// keep using the staged executor's pipelined host mode for host buffers even in peer-direct mode)
+ftar_status_t peer_allreduce_host_whole(const HostIO& io, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                                        const Plan& plan, ftar_comm* c, hipStream_t stream, int mode) {
+  const size_t bytes = count * dtype_size(dt);
+  if (bytes > c->staging_bytes) FTAR_RETURN_IF(refuse_growth_under_capture(c, "the staging buffer"));
+  FTAR_RETURN_IF(ensure_buffer(&c->staging, &c->staging_bytes, bytes, {c->h2d_s, c->comm_s, c->red_s, c->d2h_s}));
+  FTAR_CHECK_HIP(hipMemcpyAsync(c->staging, io.src, bytes, hipMemcpyHostToDevice, stream));
+  FTAR_RETURN_IF(grow_events(c, 5));
+  FTAR_RETURN_IF(peer_allreduce(nullptr, c->staging, count, dt, op, plan, c, stream, mode));
+  FTAR_CHECK_HIP(hipMemcpyAsync(io.dst, c->staging, bytes, hipMemcpyDeviceToHost, stream));
   return FTAR_SUCCESS;
 }
 

@@ -158,6 +158,30 @@ char* reg_peer(const ftar_comm::Reg* r, const void* p, int peer) {
 }
 }  // namespace
 
+// One DMA copy per segment (empty ones skipped), so the copy engines rather than CUs move the bytes: each on a
+// stream of its own forked from `s` (by *fork) and joined back into it; the streams and events grow as needed.
+static ftar_status_t dma_copies(hipStream_t s, hipEvent_t* fork, std::vector<hipStream_t>* ds,
+                                std::vector<hipEvent_t>* dj, const std::vector<Segment>& segs) {
+  if (!*fork) FTAR_CHECK_HIP(hipEventCreateWithFlags(fork, hipEventDisableTiming));
+  while (ds->size() < segs.size()) {
+    hipStream_t t;
+    hipEvent_t e;
+    FTAR_CHECK_HIP(hipStreamCreateWithFlags(&t, hipStreamNonBlocking));
+    FTAR_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ds->push_back(t);
+    dj->push_back(e);
+  }
+  FTAR_CHECK_HIP(hipEventRecord(*fork, s));
+  for (size_t i = 0; i < segs.size(); ++i) {
+    if (!segs[i].bytes) continue;
+    FTAR_CHECK_HIP(hipStreamWaitEvent((*ds)[i], *fork, 0));
+    FTAR_CHECK_HIP(hipMemcpyAsync(segs[i].dst, segs[i].src, segs[i].bytes, hipMemcpyDeviceToDevice, (*ds)[i]));
+    FTAR_CHECK_HIP(hipEventRecord((*dj)[i], (*ds)[i]));
+    FTAR_CHECK_HIP(hipStreamWaitEvent(s, (*dj)[i], 0));
+  }
+  return FTAR_SUCCESS;
+}
+
 // the peer forms' cross-GPU copies: one copy-kernel launch over every segment (every link at once), or with
 // peer_dma one DMA copy per segment, each on its own stream, all joined back into comm_s
 ftar_status_t peer_copy(ftar_comm* c, const std::vector<Segment>& segs) {
@@ -167,24 +191,7 @@ ftar_status_t peer_copy(ftar_comm* c, const std::vector<Segment>& segs) {
       if (g.bytes) FTAR_CHECK_HIP(hipMemcpyAsync(g.dst, g.src, g.bytes, hipMemcpyDeviceToDevice, c->comm_s));
     return FTAR_SUCCESS;
   }
-  if (!c->dma_fork) FTAR_CHECK_HIP(hipEventCreateWithFlags(&c->dma_fork, hipEventDisableTiming));
-  while (c->dma_s.size() < segs.size()) {
-    hipStream_t t;
-    hipEvent_t e;
-    FTAR_CHECK_HIP(hipStreamCreateWithFlags(&t, hipStreamNonBlocking));
-    FTAR_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    c->dma_s.push_back(t);
-    c->dma_ev.push_back(e);
-  }
-  FTAR_CHECK_HIP(hipEventRecord(c->dma_fork, c->comm_s));
-  for (size_t i = 0; i < segs.size(); ++i) {
-    if (!segs[i].bytes) continue;
-    FTAR_CHECK_HIP(hipStreamWaitEvent(c->dma_s[i], c->dma_fork, 0));
-    FTAR_CHECK_HIP(hipMemcpyAsync(segs[i].dst, segs[i].src, segs[i].bytes, hipMemcpyDeviceToDevice, c->dma_s[i]));
-    FTAR_CHECK_HIP(hipEventRecord(c->dma_ev[i], c->dma_s[i]));
-    FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, c->dma_ev[i], 0));
-  }
-  return FTAR_SUCCESS;
+  return dma_copies(c->comm_s, &c->dma_fork, &c->dma_s, &c->dma_ev, segs);
 }
 
 ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
@@ -207,8 +214,7 @@ ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
   const Stage& rs = plan.stages[0];
   const Stage& ag = plan.stages[1];
   hipEvent_t* ev = c->events.data();
-  FTAR_CHECK_HIP(hipEventRecord(ev[0], stream));
-  FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, ev[0], 0));
+  FTAR_RETURN_IF(fork_streams(stream, ev[0], {c->comm_s}));
   c->nmarks = 0;
   FTAR_RETURN_IF(mark(c, "start", c->comm_s));
   std::vector<Segment> segs;
@@ -290,9 +296,7 @@ ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
     }
   }
   FTAR_RETURN_IF(tp->before_join());
-  FTAR_CHECK_HIP(hipEventRecord(ev[1], c->comm_s));
-  FTAR_CHECK_HIP(hipStreamWaitEvent(stream, ev[1], 0));
-  return FTAR_SUCCESS;
+  return join_streams(stream, {{ev[1], c->comm_s}});
 }
 
 // xGMI probe (diagnostic, collective): every rank runs the same copy pattern
@@ -310,30 +314,10 @@ ftar_status_t xgmi_probe(ftar_comm* c, size_t bytes, int iters, double* out, int
   FTAR_CHECK_HIP(hipEventCreate(&e1));
   ftar_status_t st = FTAR_SUCCESS;
   const int nxt = (me + 1) % P, prv = (me + P - 1) % P;
-  // DMA modes: one hipMemcpyAsync per peer, each on its own stream (forked from and joined back into the
-  // comm stream), so the copy engines rather than CUs move the bytes
+  // DMA modes: one hipMemcpyAsync per peer (dma_copies), on streams and events of the probe's own
   std::vector<hipStream_t> ds;
   std::vector<hipEvent_t> dj;
   hipEvent_t fork = nullptr;
-  auto dma = [&](const std::vector<Segment>& segs) -> ftar_status_t {
-    if (!fork) FTAR_CHECK_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
-    while (ds.size() < segs.size()) {
-      hipStream_t t;
-      hipEvent_t e;
-      FTAR_CHECK_HIP(hipStreamCreateWithFlags(&t, hipStreamNonBlocking));
-      FTAR_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      ds.push_back(t);
-      dj.push_back(e);
-    }
-    FTAR_CHECK_HIP(hipEventRecord(fork, c->comm_s));
-    for (size_t i = 0; i < segs.size(); ++i) {
-      FTAR_CHECK_HIP(hipStreamWaitEvent(ds[i], fork, 0));
-      FTAR_CHECK_HIP(hipMemcpyAsync(segs[i].dst, segs[i].src, segs[i].bytes, hipMemcpyDeviceToDevice, ds[i]));
-      FTAR_CHECK_HIP(hipEventRecord(dj[i], ds[i]));
-      FTAR_CHECK_HIP(hipStreamWaitEvent(c->comm_s, dj[i], 0));
-    }
-    return FTAR_SUCCESS;
-  };
   // 0 local copy | 1 read from one peer | 2 read from all | 3 write to one | 4 write to all (copy kernels)
   // 5 read from all | 6 write to all (DMA engines)
   for (int mode = 0; mode < std::min(nout, 7) && st == FTAR_SUCCESS; ++mode) {
@@ -349,7 +333,8 @@ ftar_status_t xgmi_probe(ftar_comm* c, size_t bytes, int iters, double* out, int
     out[mode] = 0.0;
     if (segs.empty()) continue;
     auto copy = [&]() {
-      return mode >= 5 ? dma(segs) : launch_gather(segs.data(), (int)segs.size(), c->comm_s, true, max_wg_per_seg);
+      return mode >= 5 ? dma_copies(c->comm_s, &fork, &ds, &dj, segs)
+                       : launch_gather(segs.data(), (int)segs.size(), c->comm_s, true, max_wg_per_seg);
     };
     if ((st = copy()) != FTAR_SUCCESS) break;  // warm
     if ((st = tp->barrier(c->comm_s)) != FTAR_SUCCESS) break;

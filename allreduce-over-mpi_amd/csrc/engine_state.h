@@ -1,13 +1,16 @@
 // The communicator's state and the engine's interfaces between its translation units (not the C ABI):
-//   engine.cpp       communicator lifecycle and settings, the two-stream executor
-//   engine_api.cpp   the C ABI (bring-up, setters, entry points, in-process group calls)
-//   engine_peer.cpp  the peer-direct forms (IPC-mapped exchange buffers over xGMI) and the xGMI probe
-//   engine_host.cpp  host buffers on a host-bootstrapped communicator, the piece-pipelined read form
+//   engine.cpp         communicator lifecycle and settings, what a call runs (resolve_call) and its dispatch
+//   engine_staged.cpp  the staged two-stream executor (device buffers, host buffers on a p2p transport)
+//   engine_api.cpp     the C ABI (bring-up, setters, entry points, in-process group calls)
+//   engine_peer.cpp    the peer-direct forms (IPC-mapped exchange buffers over xGMI) and the xGMI probe
+//   engine_host.cpp    host buffers on a host-bootstrapped communicator: piece-pipelined read form, whole bucket
 #pragma once
 
+#include <algorithm>
 #include <condition_variable>
 #include <cstdint>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -134,6 +137,33 @@ ftar_status_t mark(ftar_comm* c, const std::string& name, hipStream_t s);
 ftar_status_t grow_events(ftar_comm* c, size_t n);
 // FTAR_ERR_UNSUPPORTED (with a message) when a buffer would grow under stream capture
 ftar_status_t refuse_growth_under_capture(const ftar_comm* c, const char* what);
+// grow-only device buffer; `users`: the streams whose earlier work may still touch the old one
+ftar_status_t ensure_buffer(void** buf, size_t* have, size_t need, std::initializer_list<hipStream_t> users);
+// the internal streams join a call: `ev` recorded on the caller's stream, every stream of `streams` waits for it
+ftar_status_t fork_streams(hipStream_t stream, hipEvent_t ev, std::initializer_list<hipStream_t> streams);
+// ... and leave it: every event recorded on its stream (unless it already is), then the caller's stream
+// waits for each, in the order given
+struct Join {
+  hipEvent_t ev;
+  hipStream_t s;
+  bool record = true;
+};
+ftar_status_t join_streams(hipStream_t stream, std::initializer_list<Join> joins);
+// piece k of every block: fn(first element, elements) for [b*split + k*chunk, ...) clipped to the block and to count
+template <class Fn>
+ftar_status_t for_piece(size_t P, size_t split, size_t chunk, size_t count, size_t k, Fn&& fn) {
+  for (size_t b = 0; b < P; ++b) {
+    const size_t lo = b * split + k * chunk, end = std::min(count, (b + 1) * split);
+    if (lo < end) FTAR_RETURN_IF(fn(lo, std::min(chunk, end - lo)));
+  }
+  return FTAR_SUCCESS;
+}
+
+// What one call does; call_path (engine.cpp, five rows, the first that matches wins) is the whole decision.
+// host: host buffers; p2p: Transport::async_p2p (false on a host-bootstrapped communicator); eligible:
+// peer_eligible(plan); pipeline: host_peer_pipeline; several_pieces: host_peer_piece < plan.split.
+enum class CallPath { PeerDevice, PeerHostPipelined, PeerHostWhole, Staged, Refused };
+CallPath call_path(bool host, bool p2p, int peer_mode, bool eligible, bool pipeline, bool several_pieces);
 
 // ---- engine.cpp -----------------------------------------------------------------------------------------
 // Host mode piece per block: 0 = auto (auto_host_chunk)
@@ -153,9 +183,18 @@ ftar_status_t allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_d
                         const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host = nullptr);
 // the reduce stream on `cus` CUs (0 = all); refused on RCCL communicators
 ftar_status_t set_reduce_cus(ftar_comm* c, int cus);
-// the form the explicit settings describe (ftar_form_t), or -2; set_form applies one
+// the form (ftar_form_t) a reduce-scatter, an all-gather and a peer mode make, or -2 for a mix no form names;
+// form_of: of the explicit settings; set_form applies one
+int form_for(int reduce_scatter, int allgather, int peer);
 int form_of(const ftar_comm* c);
 void set_form(ftar_comm* c, int form);
+
+// ---- engine_staged.cpp ----------------------------------------------------------------------------------
+// the plan's stages piece by piece on the comm and reduce streams; model_chunk: the execution model's piece
+// in bytes (0 = whole blocks) where none is fixed; host buffers go through the staging buffer piece by piece
+ftar_status_t staged_allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                               const Plan& plan, size_t model_chunk, ftar_comm* c, hipStream_t stream,
+                               const HostIO* host);
 
 // ---- engine_peer.cpp ------------------------------------------------------------------------------------
 // a one-round plan the peer kernels can run (one block per peer each way, all-gather straight into recvbuf)
@@ -181,7 +220,10 @@ struct HostIO {
 };
 // elements per piece of peer_allreduce_host
 size_t host_peer_piece(const ftar_comm* c, size_t split, size_t esz);
+// the read form in pieces of `chunk` elements per block (host_peer_piece), or either form on the whole bucket
 ftar_status_t peer_allreduce_host(const HostIO& io, size_t count, ftar_dtype_t dt, ftar_op_t op, const Plan& plan,
-                                  ftar_comm* c, hipStream_t stream);
+                                  ftar_comm* c, hipStream_t stream, size_t chunk);
+ftar_status_t peer_allreduce_host_whole(const HostIO& io, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                                        const Plan& plan, ftar_comm* c, hipStream_t stream, int mode);
 
 }  // namespace ftar

@@ -132,6 +132,36 @@ def test_reduce_argument_errors_without_gpu():
         ftar.reduce([1024, 2048], 4096, 10, "f32", "band")   # BAND on float: unsupported (mpi_mod.hpp:1397)
 
 
+CALL_PATHS = ("PeerDevice", "PeerHostPipelined", "PeerHostWhole", "Staged", "Refused")   # ftar::CallPath, in order
+
+
+def expected_call_path(host, p2p, peer_mode, eligible, pipeline, several_pieces):
+    """The decision table of a call, written out row by row (the first row that matches wins)."""
+    READ = 1   # FTAR_PEER_READ (0 off, 2 write)
+    rows = [
+        (not host and peer_mode != 0 and eligible, "PeerDevice"),
+        (host and peer_mode == READ and not p2p and eligible and pipeline and several_pieces, "PeerHostPipelined"),
+        (host and peer_mode != 0 and not p2p and eligible, "PeerHostWhole"),
+        (not p2p, "Refused"),
+        (True, "Staged"),
+    ]
+    return next(path for cond, path in rows if cond)
+
+
+@pytest.mark.parametrize("host", [0, 1])
+@pytest.mark.parametrize("p2p", [0, 1])
+@pytest.mark.parametrize("peer_mode", [0, 1, 2])
+@pytest.mark.parametrize("eligible", [0, 1])
+@pytest.mark.parametrize("pipeline", [0, 1])
+@pytest.mark.parametrize("several_pieces", [0, 1])
+def test_call_path_decision_table(host, p2p, peer_mode, eligible, pipeline, several_pieces):
+    """Which executor a call runs (ftar::call_path, the engine's one decision) for every combination of the
+    six facts it depends on: 2*2*3*2*2*2 = 96 cases.  No communicator, no GPU."""
+    import ftar
+    got = ftar.lib().ftar_debug_call_path(host, p2p, peer_mode, eligible, pipeline, several_pieces)
+    assert CALL_PATHS[got] == expected_call_path(host, p2p, peer_mode, eligible, pipeline, several_pieces)
+
+
 def test_cost_model_candidates_match_reference_getwidth():
     """The candidate set is the reference's getWidth(P) (tests/golden/getwidth.json, dumped from
     cost_model/GetWidth.h), its [1,P]/[P,1] entries being the ring, plus the single-stage

@@ -7,7 +7,7 @@ rank, so the association order shows in the bits.  Every rank's WHOLE output is 
 reference's fold of the P inputs, evaluated over the whole bucket on the GPU by tests/whole_fold.py (pinned to
 the oracle by tests/test_whole_fold.py).  Some cases use pipeline pieces that do not divide a block
 (FTAR_CHUNK_BYTES / the host piece size), so piece boundaries fall mid-block and every block ends on a short
-piece; in host mode the (stage, piece) steps also run skewed (engine.cpp step_order).  Every data-movement form
+piece; in host mode the (stage, piece) steps also run skewed (engine_staged.cpp step_order).  Every data-movement form
 runs at C4 (direct, stages, collective, peer-read, peer-write, auto), the peer forms at C5 too.
 """
 import pytest
