@@ -1,7 +1,7 @@
 // libftar_bench.so: the A/B harness of the reduce kernels and kernel-level test hooks, kept OUT of the
 // product library (libftar.so holds only the kernels launch_reduce / launch_tree / launch_copy /
-// launch_gather dispatch).  Not part of ftar.h; loaded by tools/kbench*.py and the bf16 conversion test
-// through ftar.bench_lib().  Shape, cache-policy and dtype variants of the production kernels in
+// launch_gather dispatch).  Not part of ftar.h; loaded by tools/kbench*.py, the bf16 conversion test and the
+// kernel-edge tests (ftar_debug_reduce_ex, ftar_debug_gather) through ftar.bench_lib().  Shape, cache-policy and dtype variants of the production kernels in
 // reduce_impl.h are instantiated here from the same templates; launch_gather (variant 90) and
 // launch_reduce (the nested-fold A/B) are the product's own, linked from libftar.so.
 #include "reduce_impl.h"
@@ -154,6 +154,28 @@ extern "C" ftar_status_t ftar_debug_reduce_nested_lds(int lds, const void* const
                                                       int dtype, const int* shape, int nlevels, void* stream) {
   return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, FTAR_SUM, static_cast<hipStream_t>(stream),
                              false, shape, nlevels, lds != 0);
+}
+
+// Test hooks of the kernel-edge tests (tests/kernel_edges.py): the product's own launchers with every argument
+// the engine can give them.  ftar_debug_reduce_ex is launch_reduce unchanged (round_each: the hop folds;
+// lds = 0: the peer forms' ":vec" dispatch and the register tree kernels; scale may be NULL).
+extern "C" ftar_status_t ftar_debug_reduce_ex(const void* const* srcs, int k, void* dst, size_t count, int dtype, int op,
+                                              int round_each, const int* shape, int nlevels, int lds,
+                                              const double* scale, void* stream) {
+  return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, (ftar_op_t)op, static_cast<hipStream_t>(stream),
+                             round_each != 0, shape, nlevels, lds != 0, scale);
+}
+
+// launch_gather on dsts[i][0..bytes[i]) = srcs[i][0..bytes[i]), i < nsegs (zero-byte segments included: the
+// launcher packs them out); nsegs outside 0..FTAR_MAX_K is the launcher's to refuse.
+extern "C" ftar_status_t ftar_debug_gather(const void* const* srcs, void* const* dsts, const size_t* bytes, int nsegs,
+                                           int nt, size_t max_wg_per_seg, int release_system, void* stream) {
+  if (nsegs < 0 || nsegs > FTAR_MAX_K) return FTAR_ERR_INVALID_ARG;
+  if (nsegs && (!srcs || !dsts || !bytes)) return FTAR_ERR_INVALID_ARG;
+  ftar::Segment segs[FTAR_MAX_K];
+  for (int i = 0; i < nsegs; ++i) segs[i] = ftar::Segment{srcs[i], dsts[i], bytes[i]};
+  return ftar::launch_gather(segs, nsegs, static_cast<hipStream_t>(stream), nt != 0, max_wg_per_seg,
+                             release_system != 0);
 }
 
 namespace ftar {

@@ -278,6 +278,29 @@ def dtype_size(dtype):
     return _lib.ftar_dtype_size(_dt(dtype))
 
 
+def _demangle_f16(name):
+    """ftar_debug_last_kernel hands back the mangled name when the C++ runtime's demangler refuses it: one older
+    than _Float16's mangling (DF16_), which the fp16 MAX / MIN kernels carry.  Demangled here with `half` (Dh, a
+    builtin code like DF16_, so no substitution moves) in its place and the spelling rocprofv3 prints put back."""
+    if not name.startswith("_Z") or "DF16_" not in name:
+        return name
+    try:
+        cxx = ctypes.CDLL("libstdc++.so.6")
+        cxx.__cxa_demangle.restype = _vp
+        cxx.__cxa_demangle.argtypes = [ctypes.c_char_p, _vp, _vp, ctypes.POINTER(_int)]
+        libc = ctypes.CDLL(None)
+        libc.free.argtypes = [_vp]
+    except (OSError, AttributeError):
+        return name
+    st = _int(0)
+    p = cxx.__cxa_demangle(name.replace("DF16_", "Dh").encode(), None, None, ctypes.byref(st))
+    if st.value != 0 or not p:
+        return name
+    out = ctypes.string_at(p).decode()
+    libc.free(p)
+    return out.replace("half", "_Float16")
+
+
 def last_kernel():
     """The kernel ftar's reduce/copy launchers last launched on this thread (ftar_debug_last_kernel), as
     kernel_symbol() of its demangled name, or None."""
@@ -286,7 +309,7 @@ def last_kernel():
         return None
     buf = ctypes.create_string_buffer(n + 1)
     _lib.ftar_debug_last_kernel(buf, n + 1)
-    return kernel_symbol(buf.value.decode())
+    return kernel_symbol(_demangle_f16(buf.value.decode()))
 
 
 # ---- L3: one-device reduce ----------------------------------------------------

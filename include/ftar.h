@@ -136,7 +136,9 @@ size_t ftar_dtype_size(ftar_dtype_t dt);
 /* ---- L3: k-way element-wise reduce on one device -------------------------
  * dst[i] = srcs[0][i] OP srcs[1][i] OP ... left to right, i < count; OP is
  * + (SUM), & (BAND), max or min (the support matrix is at ftar_op_t above).
- * srcs: HOST array of k device pointers; dst may alias srcs[0] (in place).
+ * srcs: HOST array of k device pointers; dst may be the same address as any
+ * one source (in place: every element of every source is read before that
+ * element is written); a dst that partly overlaps a source is undefined.
  * k == 1 copies (vector_add/reduce_sum.h:36-47).  stream: hipStream_t. */
 ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                           ftar_op_t op, void* stream);
@@ -147,14 +149,16 @@ ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t coun
  * level-0 results, ... each node left to right; bf16 and fp16 inner nodes
  * are rounded to their format (what a staged tree stores between its stages).
  * Integer sums, AND, MAX and MIN are associative: the result equals
- * ftar_reduce's (the flat kernel runs).  nlevels <= 1 is ftar_reduce. */
+ * ftar_reduce's (the flat kernel runs).  nlevels <= 1 is ftar_reduce.  dst
+ * may be the same address as any one source, as for ftar_reduce. */
 ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  ftar_op_t op, const int* shape, int nlevels, void* stream);
 /* Scaled SUM (extension; AVG's root fold on one device) of f32, f64, bf16 or f16: flat for nlevels <= 1,
  * nested as ftar_reduce_nested otherwise, finishing as dst = round_to_dtype(A x scale) -- A the fold's
  * accumulator before its one rounding (fp32 for bf16 / f16; a nested fold's root, its inner nodes rounded
  * as ever), scale cast to float unless the dtype is f64, one correctly rounded multiply, subnormal products
- * kept.  k == 1 is a scaled copy; dst may alias srcs[0].  A non-finite scale returns FTAR_ERR_INVALID_ARG,
+ * kept.  k == 1 is a scaled copy; dst may be the same address as any one source (partial overlap is
+ * undefined).  A non-finite scale returns FTAR_ERR_INVALID_ARG,
  * other dtypes FTAR_ERR_UNSUPPORTED, both before any device work. */
 ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  double scale, const int* shape, int nlevels, void* stream);
