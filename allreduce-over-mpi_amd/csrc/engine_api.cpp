@@ -244,6 +244,10 @@ int ftar_debug_call_path(int host, int p2p, int peer_mode, int eligible, int pip
   return (int)ftar::call_path(host != 0, p2p != 0, peer_mode, eligible != 0, pipeline != 0, several_pieces != 0);
 }
 
+// Test hook (not in ftar.h): the size an exportable buffer of `bytes` is allocated with (ftar::ipc_safe_size_for),
+// with the runtime's bit-31 size guard on or off.
+size_t ftar_debug_ipc_safe_size(size_t bytes, int guard) { return ftar::ipc_safe_size_for(bytes, guard != 0); }
+
 // Test/tuning hook (not in ftar.h): peer-form copies nontemporal (nt) or not,
 // fold through the LDS-staged kernel (lds) or the register kernel.
 ftar_status_t ftar_debug_set_peer_tuning(ftar_comm_t comm, int nt, int lds) {

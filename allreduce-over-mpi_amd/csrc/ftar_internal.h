@@ -219,7 +219,7 @@ ftar_status_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t 
 size_t dtype_size(ftar_dtype_t dt);
 
 // ---------------------------------------------------------------------------
-// transports (transport.cpp)
+// transports (transport_rccl.cpp, transport_local.cpp, transport_host.cpp; their IPC plumbing: ipc.cpp)
 // ---------------------------------------------------------------------------
 class Transport {
  public:
@@ -348,6 +348,7 @@ ftar_status_t ipc_export(const void* p, IpcRef* out);
 // around them (ipc_safe_size).
 bool ipc_size_guard();
 size_t ipc_safe_size(size_t bytes);
+size_t ipc_safe_size_for(size_t bytes, bool guard);  // the rounding rule itself: ipc_safe_size with the guard given
 // A device buffer of `bytes` for IPC export (ipc = true: rounded by
 // ipc_safe_size and export-checked; an allocation whose export fails -- a
 // fresh hipMalloc landing on a recently closed IPC mapping can -- is set aside

@@ -202,6 +202,8 @@ _lib.ftar_comm_get_allgather.argtypes = [_vp, ctypes.POINTER(_int)]
 _lib.ftar_plan_json.restype = ctypes.c_long
 _lib.ftar_debug_last_kernel.argtypes = [ctypes.c_char_p, _sz]
 _lib.ftar_debug_last_kernel.restype = ctypes.c_long
+_lib.ftar_debug_ipc_safe_size.argtypes = [_sz, _int]
+_lib.ftar_debug_ipc_safe_size.restype = _sz
 
 
 def lib():

@@ -163,6 +163,31 @@ def test_call_path_decision_table(host, p2p, peer_mode, eligible, pipeline, seve
     assert CALL_PATHS[got] == expected_call_path(host, p2p, peer_mode, eligible, pipeline, several_pieces)
 
 
+MIB, GIB = 1 << 20, 1 << 30
+
+
+@pytest.mark.parametrize("nbytes,guard,expected", [
+    (0, 0, 2 * MIB), (0, 1, 2 * MIB),
+    (1, 0, 2 * MIB), (1, 1, 2 * MIB),
+    (2 * MIB, 0, 2 * MIB), (2 * MIB, 1, 2 * MIB),
+    (2 * MIB + 1, 0, 2 * MIB + 1), (2 * MIB + 1, 1, 2 * MIB + 1),
+    (2 * GIB - 1, 0, 2 * GIB - 1), (2 * GIB - 1, 1, 2 * GIB - 1),
+    (2 * GIB, 1, 4 * GIB),
+    (2 * GIB, 0, 2 * GIB),
+    (3 * GIB, 1, 4 * GIB),
+    (4 * GIB, 1, 4 * GIB),
+    (4 * GIB + 1, 1, 4 * GIB + 1),
+    (6 * GIB, 1, 8 * GIB),
+    (8 * GIB - 1, 1, 8 * GIB),
+])
+def test_ipc_safe_size_rounding(nbytes, guard, expected):
+    """The size an exportable buffer is allocated with (ftar::ipc_safe_size_for): at least 2 MiB, and with the
+    runtime's size guard on, a size with bit 31 set goes up to the next multiple of 4 GiB.  No communicator,
+    no GPU."""
+    import ftar
+    assert ftar.lib().ftar_debug_ipc_safe_size(nbytes, guard) == expected
+
+
 def test_cost_model_candidates_match_reference_getwidth():
     """The candidate set is the reference's getWidth(P) (tests/golden/getwidth.json, dumped from
     cost_model/GetWidth.h), its [1,P]/[P,1] entries being the ring, plus the single-stage
