@@ -125,6 +125,16 @@ hipError_t hop_variant(int v, const void* const* srcs, int k, void* dst, size_t 
   return hipErrorInvalidValue;
 }
 
+// the fp8 A/B (profiles/f8/): the (U, W) shapes 40-62 at k = 2 and 8 for one fp8 trait
+template <class Tr>
+hipError_t f8_variant(int v, const void* const* srcs, int k, void* dst, size_t nvec, hipStream_t s) {
+  switch (k) {
+    case 2: return variant_prog<Tr, 2>(v, srcs, dst, nvec, s);
+    case 8: return variant_prog<Tr, 8>(v, srcs, dst, nvec, s);
+  }
+  return hipErrorInvalidValue;
+}
+
 }  // namespace ftar
 
 extern "C" ftar_status_t ftar_debug_reduce_variant(int variant, int dtype, const void* const* srcs, int k, void* dst,
@@ -144,6 +154,14 @@ extern "C" ftar_status_t ftar_debug_reduce_variant(int variant, int dtype, const
   // (variants 40-62, k = 2 and 8) for fp16 SUM, u16 SUM, 200 + f16 / 200 + i16 = MAX, and 300 + f16 = fp16 MAX by
   // integer keys (sign-magnitude flipped to two's complement per packed half, v_pk_max_i16, NaN lanes collected
   // apart); dropped to keep build time.)
+  // e4m3 (e5m2 runs the same instructions under other opcodes): the SUM, 200 + e4m3 = MAX as production does it
+  // (widen, fp32 maximum, narrow), 300 + e4m3 = MAX by integer keys on the bytes (F8KeyMinMax); k = 2 and 8
+  else if (dtype == FTAR_FLOAT8_E4M3 && count % 16 == 0)
+    e = ftar::f8_variant<ftar::E4M3Sum>(variant, srcs, k, dst, count / 16, s);
+  else if (dtype == 200 + FTAR_FLOAT8_E4M3 && count % 16 == 0)
+    e = ftar::f8_variant<ftar::F8MinMax<ftar::E4M3Fmt, true>>(variant, srcs, k, dst, count / 16, s);
+  else if (dtype == 300 + FTAR_FLOAT8_E4M3 && count % 16 == 0)
+    e = ftar::f8_variant<ftar::F8KeyMinMax<false, true>>(variant, srcs, k, dst, count / 16, s);
   else return FTAR_ERR_INVALID_ARG;
   return e == hipSuccess ? FTAR_SUCCESS : FTAR_ERR_HIP;
 }
@@ -327,6 +345,152 @@ extern "C" ftar_status_t ftar_debug_f16_cvt_check(unsigned long long* mismatches
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
         hipMemcpy(mismatches, d_bad, 2 * sizeof *d_bad, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(first, d_first, 2 * sizeof *d_first, hipMemcpyDeviceToHost) != hipSuccess)
+      st = FTAR_ERR_HIP;
+  }
+  ftar::hip_ignore(hipFree(d_bad));
+  ftar::hip_ignore(hipFree(d_first));
+  return st;
+}
+
+namespace ftar {
+namespace {
+// fp32 -> OCP fp8 in integer arithmetic, the specification of the fp8 sums' rounding (ftar.h): RNE on the
+// encoding with MB mantissa bits and exponent bias BIAS (e4m3: 3, 7; e5m2: 2, 15), the mantissa carry running
+// into the next encoding, no saturation.  What lies above the largest finite encoding after rounding is the
+// format's overflow: e5m2's inf (0x7c), e4m3's NaN (0x7f) -- for an fp32 inf too; a NaN gives 0x7f.
+template <int MB, int BIAS>
+__host__ __device__ constexpr unsigned f8_rne_bits(unsigned u) {
+  const unsigned sign = (u >> 24) & 0x80u, a = u & 0x7fffffffu;
+  constexpr unsigned kOver = MB == 3 ? 0x7fu : 0x7cu;  // the encoding right above the largest finite one
+  if (a > 0x7f800000u) return sign | 0x7fu;
+  constexpr int sh = 23 - MB;                                     // mantissa bits dropped
+  constexpr unsigned min_normal = (unsigned)(127 - BIAS + 1) << 23;  // 2^(1 - BIAS)
+  if (a >= min_normal) {
+    if (a >= 0x7f800000u) return sign | kOver;
+    const unsigned r = a - ((unsigned)(127 - BIAS) << 23);       // exponent rebias
+    const unsigned q = (r + ((1u << (sh - 1)) - 1u) + ((r >> sh) & 1u)) >> sh;  // a carry bumps the exponent
+    return sign | (q >= kOver ? kOver : q);
+  }
+  const unsigned e = a >> 23, m = (a & 0x7fffffu) | 0x800000u;  // value = m x 2^(e - 150); one ulp = 2^(1 - BIAS - MB)
+  const unsigned shift = (unsigned)(151 - BIAS - MB) - e;        // h = value / ulp = m >> shift
+  if (e == 0 || shift > 25u) return sign;                        // below half the smallest subnormal: zero
+  const unsigned h = m >> shift, rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  return sign | (h + ((rem > half || (rem == half && (h & 1u))) ? 1u : 0u));
+}
+// OCP fp8 -> fp32 by integer expansion (exact); e5m2's all-ones exponent is inf / NaN, e4m3's only NaN is 0x7f
+template <int MB, int BIAS>
+__host__ __device__ constexpr unsigned f8_widen_bits(unsigned b) {
+  const unsigned sign = (b & 0x80u) << 24, e = (b & 0x7fu) >> MB, m = b & ((1u << MB) - 1u);
+  if (MB == 3 ? (b & 0x7fu) == 0x7fu : e == 31u) return sign | 0x7f800000u | (m << (23 - MB));
+  if (e) return sign | ((e + 127u - BIAS) << 23) | (m << (23 - MB));
+  if (!m) return sign;
+  int p = MB - 1;  // the leading one of a subnormal: value = m x 2^(1 - BIAS - MB)
+  while (!((m >> p) & 1u)) --p;
+  return sign | ((unsigned)(p + 128 - BIAS - MB) << 23) | ((m << (23 - p)) & 0x7fffffu);
+}
+// 16 + 1 -> 16 and 18 + 1 -> 20 (ties to even), 448, 464 -> 448 (a tie: 448's mantissa is even), 464 + -> NaN,
+// inf -> NaN, the smallest subnormal 2^-9 and half of it (a tie to zero), the carry from the subnormals into
+// the normals
+static_assert(f8_rne_bits<3, 7>(0x41880000u) == 0x58u && f8_rne_bits<3, 7>(0x41980000u) == 0x5au &&
+              f8_rne_bits<3, 7>(0x43e00000u) == 0x7eu && f8_rne_bits<3, 7>(0x43e7ffffu) == 0x7eu &&
+              f8_rne_bits<3, 7>(0x43e80000u) == 0x7eu && f8_rne_bits<3, 7>(0x43e80001u) == 0x7fu &&
+              f8_rne_bits<3, 7>(0xff800000u) == 0xffu &&
+              f8_rne_bits<3, 7>(0x3b000000u) == 0x01u && f8_rne_bits<3, 7>(0x3a800000u) == 0x00u &&
+              f8_rne_bits<3, 7>(0x3a800001u) == 0x01u && f8_rne_bits<3, 7>(0x3c780000u) == 0x08u &&
+              f8_rne_bits<3, 7>(0x3f800000u) == 0x38u);
+// e5m2: 57344, 61440 - -> 57344, 61440 -> inf, inf -> inf, 1, the smallest subnormal 2^-16, half of it -> 0
+static_assert(f8_rne_bits<2, 15>(0x47600000u) == 0x7bu && f8_rne_bits<2, 15>(0x476fffffu) == 0x7bu &&
+              f8_rne_bits<2, 15>(0x47700000u) == 0x7cu && f8_rne_bits<2, 15>(0x7f800000u) == 0x7cu &&
+              f8_rne_bits<2, 15>(0x3f800000u) == 0x3cu && f8_rne_bits<2, 15>(0x37800000u) == 0x01u &&
+              f8_rne_bits<2, 15>(0x37000000u) == 0x00u && f8_rne_bits<2, 15>(0xb7000001u) == 0x81u);
+static_assert(f8_widen_bits<3, 7>(0x38u) == 0x3f800000u && f8_widen_bits<3, 7>(0x01u) == 0x3b000000u &&
+              f8_widen_bits<3, 7>(0x7eu) == 0x43e00000u && f8_widen_bits<3, 7>(0x87u) == 0xbc600000u &&
+              f8_widen_bits<2, 15>(0x3cu) == 0x3f800000u && f8_widen_bits<2, 15>(0x01u) == 0x37800000u &&
+              f8_widen_bits<2, 15>(0xfcu) == 0xff800000u && f8_widen_bits<2, 15>(0x7bu) == 0x47600000u);
+
+template <bool E5M2>
+__device__ __forceinline__ bool f8_is_nan(unsigned b) {
+  return E5M2 ? (b & 0x7fu) > 0x7cu : (b & 0x7fu) == 0x7fu;
+}
+template <bool E5M2>
+__device__ __forceinline__ bool f8_bits_differ(unsigned got, unsigned want) {  // 8-bit patterns
+  const bool ng = f8_is_nan<E5M2>(got), nw = f8_is_nan<E5M2>(want);
+  return ng != nw || (!nw && got != want);
+}
+// every float bit pattern u, in each of the four byte positions of the production packing (F8Fmt::pack: the
+// v_fin of the fp8 traits; the other three positions hold u ^ 0x80000001 and two neighbours) and through the
+// scalar narrowing (their s_fin), against the integer RNE
+template <bool E5M2>
+__global__ void __launch_bounds__(256) f8_narrow_check_kernel(unsigned long long* bad, unsigned* first) {
+  using F = F8Fmt<E5M2>;
+  constexpr int MB = E5M2 ? 2 : 3, BIAS = E5M2 ? 15 : 7;
+  const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+  unsigned long long mine = 0;
+  unsigned first_mine = 0xffffffffu;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < (1ull << 32); i += stride) {
+    const unsigned u = (unsigned)i, v[4] = {u, u ^ 0x80000001u, u + 1u, u ^ 0x00400000u};
+    const unsigned got = F::pack(f32x4{__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]),
+                                       __uint_as_float(v[3])});
+    bool differ = f8_bits_differ<E5M2>(F::narrow(__uint_as_float(u)), f8_rne_bits<MB, BIAS>(u));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) differ |= f8_bits_differ<E5M2>((got >> (8 * j)) & 0xffu, f8_rne_bits<MB, BIAS>(v[j]));
+    if (differ) {
+      ++mine;
+      first_mine = first_mine < u ? first_mine : u;
+    }
+  }
+  if (mine) {
+    atomicAdd(bad, mine);
+    atomicMin(first, first_mine);
+  }
+}
+// every byte b, in each of the four byte positions of the production widening (F8Fmt::unpack: the v_init of the
+// fp8 traits) and through the scalar one (their s_init), against the integer expansion
+template <bool E5M2>
+__global__ void __launch_bounds__(256) f8_widen_check_kernel(unsigned long long* bad, unsigned* first) {
+  using F = F8Fmt<E5M2>;
+  constexpr int MB = E5M2 ? 2 : 3, BIAS = E5M2 ? 15 : 7;
+  const unsigned b = threadIdx.x, v[4] = {b, b ^ 0x81u, (b + 1u) & 0xffu, b ^ 0x40u};
+  const f32x4 w = F::unpack(v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24));
+  auto differ = [](float got, unsigned want) {
+    const unsigned gb = __float_as_uint(got);
+    const bool ng = (gb & 0x7fffffffu) > 0x7f800000u, nw = (want & 0x7fffffffu) > 0x7f800000u;
+    return ng != nw || (!nw && gb != want);
+  };
+  if (differ(w.x, f8_widen_bits<MB, BIAS>(v[0])) || differ(w.y, f8_widen_bits<MB, BIAS>(v[1])) ||
+      differ(w.z, f8_widen_bits<MB, BIAS>(v[2])) || differ(w.w, f8_widen_bits<MB, BIAS>(v[3])) ||
+      differ(F::widen((unsigned char)b), f8_widen_bits<MB, BIAS>(b))) {
+    atomicAdd(bad, 1ull);
+    atomicMin(first, b);
+  }
+}
+}  // namespace
+}  // namespace ftar
+
+// Test hook (not in ftar.h), the sibling of ftar_debug_f16_cvt_check for the two OCP fp8 formats.  mismatches[0]
+// / [1] = how many of the 2^32 float bit patterns the production narrowing to e4m3 / e5m2 (v_cvt_pk_fp8_f32 /
+// v_cvt_pk_bf8_f32 in every byte position, and the scalar form of the element-wise paths) converts differently
+// from the integer RNE above; mismatches[2] / [3] = how many of the 2^8 bytes of e4m3 / e5m2 widen differently
+// from the integer expansion; first[0..3] = the first such pattern of each (0xffffffff: none).  NaNs compare as
+// NaN or not.
+extern "C" ftar_status_t ftar_debug_f8_cvt_check(unsigned long long* mismatches, unsigned* first) {
+  if (!mismatches || !first) return FTAR_ERR_INVALID_ARG;
+  unsigned long long* d_bad = nullptr;
+  unsigned* d_first = nullptr;
+  ftar_status_t st = FTAR_SUCCESS;  // both buffers are freed on every path below
+  if (hipMalloc(&d_bad, 4 * sizeof *d_bad) != hipSuccess || hipMalloc(&d_first, 4 * sizeof *d_first) != hipSuccess)
+    st = FTAR_ERR_NO_MEMORY;
+  if (st == FTAR_SUCCESS && (hipMemset(d_bad, 0, 4 * sizeof *d_bad) != hipSuccess ||
+                             hipMemset(d_first, 0xff, 4 * sizeof *d_first) != hipSuccess))
+    st = FTAR_ERR_HIP;
+  if (st == FTAR_SUCCESS) {
+    hipLaunchKernelGGL(ftar::f8_narrow_check_kernel<false>, dim3(8192), dim3(256), 0, nullptr, d_bad, d_first);
+    hipLaunchKernelGGL(ftar::f8_narrow_check_kernel<true>, dim3(8192), dim3(256), 0, nullptr, d_bad + 1, d_first + 1);
+    hipLaunchKernelGGL(ftar::f8_widen_check_kernel<false>, dim3(1), dim3(256), 0, nullptr, d_bad + 2, d_first + 2);
+    hipLaunchKernelGGL(ftar::f8_widen_check_kernel<true>, dim3(1), dim3(256), 0, nullptr, d_bad + 3, d_first + 3);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(mismatches, d_bad, 4 * sizeof *d_bad, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(first, d_first, 4 * sizeof *d_first, hipMemcpyDeviceToHost) != hipSuccess)
       st = FTAR_ERR_HIP;
   }
   ftar::hip_ignore(hipFree(d_bad));

@@ -118,7 +118,7 @@ struct ReduceItem {
   size_t off;                   // element offset of the block in dst
   size_t len;                   // elements (> 0)
   std::vector<Operand> srcs;    // fold order: dst = ((srcs[0] OP srcs[1]) OP srcs[2]) ...
-  bool round_each = false;      // bf16, fp16: round after every add (one hop per add)
+  bool round_each = false;      // bf16, fp16, fp8: round after every add (one hop per add)
   std::vector<int> shape;       // nested fold of srcs (launch_reduce); empty = flat
   // the block's root fold: the reduce that produces the block's final value on the rank that owns it
   // after the reduce-scatter (mark_root, schedule.cpp).  AVG scales there, and nowhere else.
@@ -163,8 +163,8 @@ ftar_status_t check_world(const Topology& t, int nranks, size_t count, Form form
 // product == k, at most kMaxFoldLevels levels; bf16 and fp16 inner nodes rounded);
 // nlevels <= 1 = flat.  Only float sums depend on it: integer sums, AND, MAX and
 // MIN are associative and take the flat kernel.
-// scale (SUM of f32, f64, bf16, fp16 only; else FTAR_ERR_UNSUPPORTED): the fold finishes as
-// round_to_dtype(A * r), A its accumulator before the one rounding (fp32 for the 16-bit floats; a nested
+// scale (SUM of f32, f64, bf16, fp16, fp8 only; else FTAR_ERR_UNSUPPORTED): the fold finishes as
+// round_to_dtype(A * r), A its accumulator before the one rounding (fp32 for the 16- and 8-bit floats; a nested
 // fold's root, inner nodes rounded as ever), r = *scale cast to float (f64: as it is); round_each folds
 // then round before each add, so the last sum reaches the multiply unrounded; k == 1 is a scaled copy.
 // op = FTAR_AVG is refused here: the engine runs it as SUM with a scale on root items (root_scale).
@@ -173,7 +173,12 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
                             hipStream_t stream, bool round_each = false, const int* shape = nullptr,
                             int nlevels = 0, bool lds = true, const double* scale = nullptr);
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op);  // the AllReduce entry points' matrix (AVG included)
-bool dtype_scalable(ftar_dtype_t dt);                    // the four float dtypes
+bool dtype_scalable(ftar_dtype_t dt);                    // the six float dtypes
+// launch_reduce's fp8 half (reduce_f8.hip, a translation unit of its own: it compiles beside
+// reduce_kernels.hip); arguments already checked, k >= 1, count > 0, op one of SUM, MAX, MIN
+ftar_status_t launch_reduce_f8(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                               hipStream_t stream, bool round_each, const int* shape, int nlevels, bool lds,
+                               const double* scale);
 // AVG on the engine's folds: the op the kernels run (SUM) and the scale of item r (1 / P as a float, f64:
 // as a double, on root items; none elsewhere).  Other ops pass through.
 struct FoldOp {

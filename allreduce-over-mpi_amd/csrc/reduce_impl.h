@@ -27,13 +27,13 @@
 //       float/double in their own precision (no FMA: pure adds),
 //       narrow integers wrap (promotion + truncating store == modular add),
 //       bool sum = OR of non-zero;
-//   * extensions (no reference): bf16 and fp16 sums = fp32 accumulate + one RNE per
+//   * extensions (no reference): bf16, fp16 and OCP fp8 (e4m3, e5m2) sums = fp32 accumulate + one RNE per
 //     reduce; MAX / MIN = signed or unsigned integer compare, IEEE 754-2019
 //     maximum / minimum on floats (exact: every fold order gives the same bits); the scaled float sums
 //     (AVG's root fold, ftar_reduce_scaled): the accumulator times r before the fold's one rounding --
 //     one body per kernel family, two finishes (PlainFin / ScaledFin below).
 #pragma once
-// Internal: the reduce kernels, their traits and launchers, included by reduce_kernels.hip (the
+// Internal: the reduce kernels, their traits and launchers, included by reduce_kernels.hip and reduce_f8.hip (the
 // production dispatch, libftar.so) and bench_kernels.hip (the A/B harness, libftar_bench.so);
 // anonymous namespace: each TU instantiates what it uses.
 #include <hip/hip_runtime.h>
@@ -316,6 +316,89 @@ using F16Sum = H16SumT<HalfFmt>;
 using F16SumHop = H16SumHopT<HalfFmt>;
 using BF16SumHopPre = H16SumHopPreT<Bf16Fmt<kHwBf16>>;
 using F16SumHopPre = H16SumHopPreT<HalfFmt>;
+// The two OCP fp8 formats (extensions): e4m3fn (bias 7, no inf, NaN = 0x7f / 0xff, max 448) and e5m2 (bias 15,
+// IEEE-like, max 57344), four elements to a dword, through gfx950's packed conversions.  Widening
+// (v_cvt_pk_f32_fp8 / _bf8, SDWA WORD_1 for bytes 2-3) is exact, subnormals included.  Narrowing
+// (v_cvt_pk_fp8_f32 / _bf8_f32, op_sel for the high half, no clamp) is RNE on the encoding with the mantissa
+// carry running into the next encoding and no saturation: e5m2 overflows to +-inf at |A| >= 61440, e4m3 to NaN
+// at |A| > 464 (and for +-inf), NaN stays NaN -- torch's float32 -> float8 cast.  The bare instructions are
+// used as they are: both directions equal the integer reference on every bit pattern (2^32 floats, 2^8 bytes;
+// ftar_debug_f8_cvt_check in bench_kernels.hip, tests/test_gpu_f8.py), so no select sits around them.
+template <bool E5M2>
+struct F8Fmt {
+  template <bool HI>
+  __device__ static f32x2 widen2(unsigned w) {  // bytes 0-1 (HI: 2-3) of w
+    if constexpr (E5M2) return __builtin_amdgcn_cvt_pk_f32_bf8(w, HI);
+    else return __builtin_amdgcn_cvt_pk_f32_fp8(w, HI);
+  }
+  template <bool HI>
+  __device__ static unsigned narrow2(float a, float b, unsigned old) {  // into bytes 0-1 (HI: 2-3) of old
+    if constexpr (E5M2) return __builtin_amdgcn_cvt_pk_bf8_f32(a, b, old, HI);
+    else return __builtin_amdgcn_cvt_pk_fp8_f32(a, b, old, HI);
+  }
+  __device__ static float widen(unsigned char b) { return widen2<false>(b).x; }
+  __device__ static unsigned char narrow(float f) { return (unsigned char)narrow2<false>(f, f, 0u); }
+  __device__ static f32x4 unpack(unsigned w) {
+    const f32x2 lo = widen2<false>(w), hi = widen2<true>(w);
+    return f32x4{lo.x, lo.y, hi.x, hi.y};
+  }
+  __device__ static unsigned pack(f32x4 v) { return narrow2<true>(v.z, v.w, narrow2<false>(v.x, v.y, 0u)); }
+  __device__ static float rnd(float f) { return widen(narrow(f)); }
+  __device__ static f32x4 rnd4(f32x4 v) { return unpack(pack(v)); }
+};
+using E4M3Fmt = F8Fmt<false>;
+using E5M2Fmt = F8Fmt<true>;
+// fp8 sums: the 16-bit floats' rules (fp32 accumulate, one RNE to the format per reduce call) on 16 elements
+// per 16-byte vector.  A family of its own beside H16SumT: that one's two-f32x4 accumulator and pair-of-words
+// unpack are spelled out in its bodies, and its generated code stays as it is.
+template <class F>
+struct F8SumT {
+  using S = unsigned char;
+  using SA = float;
+  struct VA {
+    f32x4 a, b, c, d;  // the four dwords of the vector, widened
+  };
+  __device__ static SA s_init(S x) { return F::widen(x); }
+  __device__ static SA s_comb(SA a, S x) { return a + F::widen(x); }
+  __device__ static S s_fin(SA a) { return F::narrow(a); }
+  __device__ static VA v_init(u32x4 x) { return {F::unpack(x.x), F::unpack(x.y), F::unpack(x.z), F::unpack(x.w)}; }
+  __device__ static VA v_comb(VA a, u32x4 x) { return v_add(a, v_init(x)); }
+  __device__ static u32x4 v_fin(VA a) { return u32x4{F::pack(a.a), F::pack(a.b), F::pack(a.c), F::pack(a.d)}; }
+  // nested folds: an inner node is stored in the format by the staged schedule, so it is rounded
+  __device__ static SA s_add(SA a, SA b) { return a + b; }
+  __device__ static SA s_rnd(SA a) { return F::rnd(a); }
+  __device__ static VA v_add(VA a, VA b) { return {a.a + b.a, a.b + b.b, a.c + b.c, a.d + b.d}; }
+  __device__ static VA v_rnd(VA a) { return {F::rnd4(a.a), F::rnd4(a.b), F::rnd4(a.c), F::rnd4(a.d)}; }
+  using SC = float;  // the fp32 accumulator times r, then the fold's one RNE
+  __device__ static SA s_scale(SA a, SC r) {  // as H16SumT::s_scale: the product is a value of its own in a
+    float p = mul_rn(a, r);                   // register before the conversion reads it
+    asm volatile("" : "+v"(p));
+    return p;
+  }
+  __device__ static VA v_scale(VA a, SC r) { return {mul_rn(a.a, r), mul_rn(a.b, r), mul_rn(a.c, r), mul_rn(a.d, r)}; }
+};
+// the ring's one-round fold: rounded after every add (H16SumHopT), or, under a scaled finish, before each add
+// (H16SumHopPreT)
+template <class F>
+struct F8SumHopT : F8SumT<F> {
+  using B = F8SumT<F>;
+  using typename B::S;
+  using typename B::SA;
+  using typename B::VA;
+  __device__ static SA s_comb(SA a, S x) { return F::rnd(a + F::widen(x)); }
+  __device__ static VA v_comb(VA a, u32x4 x) { return B::v_rnd(B::v_add(a, B::v_init(x))); }
+};
+template <class F>
+struct F8SumHopPreT : F8SumT<F> {
+  using B = F8SumT<F>;
+  using typename B::S;
+  using typename B::SA;
+  using typename B::VA;
+  __device__ static SA s_comb(SA a, S x) { return F::rnd(a) + F::widen(x); }
+  __device__ static VA v_comb(VA a, u32x4 x) { return B::v_add(B::v_rnd(a), B::v_init(x)); }
+};
+using E4M3Sum = F8SumT<E4M3Fmt>;
+using E5M2Sum = F8SumT<E5M2Fmt>;
 // modular integer sums on packed lanes (SWAR for 8/16-bit lanes)
 template <class S_, unsigned HI>
 struct SwarSum {
@@ -437,6 +520,68 @@ struct BF16MinMax {
   }
   __device__ static u32x4 v_fin(VA a) {
     return u32x4{pack(a.lo.x, a.lo.y), pack(a.lo.z, a.lo.w), pack(a.hi.x, a.hi.y), pack(a.hi.z, a.hi.w)};
+  }
+};
+// fp8 MAX / MIN, production: widen, fp32 maximum / minimum (v_maximum3_f32: two sources per instruction),
+// narrow.  The round trip is exact (every fp8 value is an fp32 value and narrows back to its own byte), an
+// fp32 NaN narrows to a NaN of the format, and e5m2's infs are ordinary values on both sides.
+template <class F, bool MAX>
+struct F8MinMax {
+  using B = F8SumT<F>;
+  using S = unsigned char;
+  using SA = float;
+  using VA = typename B::VA;
+  __device__ static SA s_init(S x) { return F::widen(x); }
+  __device__ static SA s_comb(SA a, S x) { return min_max<MAX, true>(a, F::widen(x)); }
+  __device__ static S s_fin(SA a) { return F::narrow(a); }
+  __device__ static VA v_init(u32x4 x) { return B::v_init(x); }
+  __device__ static VA v_comb(VA a, u32x4 x) {
+    const VA b = B::v_init(x);
+    return {min_max<MAX, true>(a.a, b.a), min_max<MAX, true>(a.b, b.b), min_max<MAX, true>(a.c, b.c),
+            min_max<MAX, true>(a.d, b.d)};
+  }
+  __device__ static u32x4 v_fin(VA a) { return B::v_fin(a); }
+};
+// The other formulation, kept as the A/B variant (bench_kernels.hip; DESIGN §4 has the rates): monotone
+// unsigned keys on the bytes -- negatives all bits flipped, non-negatives the sign bit set -- four to a dword
+// (SWAR), reduced as unsigned bytes; NaN sources (e4m3: |b| == 0x7f, e5m2: |b| > 0x7c) are collected apart
+// in bit 7 of their byte and turn the lane into 0x7f / 0xff at the end.
+template <bool E5M2, bool MAX>
+struct F8KeyMinMax {
+  using S = unsigned char;
+  using SA = unsigned;  // bits 0-7 the key, bit 8 a NaN seen
+  typedef unsigned char u8x16 __attribute__((ext_vector_type(16)));
+  struct VA {
+    u32x4 key, nan;
+  };
+  static constexpr unsigned kNanAdd = E5M2 ? 0x03u : 0x01u;  // (|b| + kNanAdd) reaches bit 7 exactly for a NaN
+  __device__ static SA s_init(S x) {
+    const unsigned b = x;
+    return ((b & 0x80u) ? (~b & 0xffu) : (b | 0x80u)) | ((((b & 0x7fu) + kNanAdd) & 0x80u) << 1);
+  }
+  __device__ static SA s_comb(SA a, S x) {
+    const SA b = s_init(x);
+    const unsigned ka = a & 0xffu, kb = b & 0xffu;
+    return ((a | b) & 0x100u) | (MAX ? (ka > kb ? ka : kb) : (ka < kb ? ka : kb));
+  }
+  __device__ static S s_fin(SA a) {
+    const unsigned k = a & 0xffu, b = (k & 0x80u) ? (k ^ 0x80u) : (~k & 0xffu);
+    return (S)((a & 0x100u) ? (b | 0x7fu) : b);
+  }
+  // x ^ (0xff where the byte's `neg` bit (bit 0) is set, 0x80 elsewhere): bits -> key with neg = the sign, key ->
+  // bits with neg = the key's top bit inverted
+  __device__ static u32x4 flip(u32x4 x, u32x4 neg) { return x ^ (((neg << 8) - neg) | 0x80808080u); }
+  __device__ static VA v_init(u32x4 x) {
+    return {flip(x, (x >> 7) & 0x01010101u), ((x & 0x7f7f7f7fu) + kNanAdd * 0x01010101u) & 0x80808080u};
+  }
+  __device__ static VA v_comb(VA a, u32x4 x) {
+    const VA b = v_init(x);
+    const u8x16 ka = __builtin_bit_cast(u8x16, a.key), kb = __builtin_bit_cast(u8x16, b.key);
+    return {__builtin_bit_cast(u32x4, min_max<MAX, false>(ka, kb)), a.nan | b.nan};
+  }
+  __device__ static u32x4 v_fin(VA a) {
+    const u32x4 n = a.nan >> 7;  // a NaN byte: 0x7f ORed in
+    return flip(a.key, (~a.key >> 7) & 0x01010101u) | ((n << 7) - n);
   }
 };
 
@@ -1244,7 +1389,7 @@ hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const
   }
 }
 
-// HOT: the largest k with an unrolled LDS-staged kernel (fp32/bf16 16, the other types 8; 0 = k = 2
+// HOT: the largest k with an unrolled LDS-staged kernel (fp32/bf16/fp16 16, the other types, fp8 included, 8; 0 = k = 2
 // only); larger k take the runtime-k register kernel.  The other types gained 4-6 % at k = 8 on the
 // LDS kernel (tools/dtype_rates.py, profiles/r02/s4/dtype_rates*.log).
 template <class Tr, int HOT, bool SC = false>

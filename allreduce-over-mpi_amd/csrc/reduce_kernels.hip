@@ -12,7 +12,7 @@ namespace ftar {
 
 size_t dtype_size(ftar_dtype_t dt) {
   switch (dt) {
-    case FTAR_UINT8: case FTAR_INT8: case FTAR_BOOL: return 1;
+    case FTAR_UINT8: case FTAR_INT8: case FTAR_BOOL: case FTAR_FLOAT8_E4M3: case FTAR_FLOAT8_E5M2: return 1;
     case FTAR_UINT16: case FTAR_INT16: case FTAR_BFLOAT16: case FTAR_FLOAT16: return 2;
     case FTAR_INT32: case FTAR_FLOAT32: return 4;
     case FTAR_INT64: case FTAR_FLOAT64: return 8;
@@ -21,7 +21,8 @@ size_t dtype_size(ftar_dtype_t dt) {
 }
 
 bool dtype_scalable(ftar_dtype_t dt) {
-  return dt == FTAR_FLOAT32 || dt == FTAR_FLOAT64 || dt == FTAR_BFLOAT16 || dt == FTAR_FLOAT16;
+  return dt == FTAR_FLOAT32 || dt == FTAR_FLOAT64 || dt == FTAR_BFLOAT16 || dt == FTAR_FLOAT16 ||
+         dt == FTAR_FLOAT8_E4M3 || dt == FTAR_FLOAT8_E5M2;
 }
 
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op) {
@@ -134,6 +135,7 @@ hipError_t tr_min_max(ftar_dtype_t dt, bool lds, const void* const* srcs, int k,
     case FTAR_FLOAT64: return tr<MinMax<double, MAX>, 8>(lds, srcs, k, dst, count, s);
     case FTAR_BFLOAT16: return tr<BF16MinMax<MAX>, 16>(lds, srcs, k, dst, count, s);
     case FTAR_FLOAT16: return tr<MinMax<_Float16, MAX>, 16>(lds, srcs, k, dst, count, s);
+    case FTAR_FLOAT8_E4M3: case FTAR_FLOAT8_E5M2: break;  // launch_reduce_f8
     case FTAR_BOOL: break;
   }
   return hipErrorInvalidValue;
@@ -200,6 +202,8 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
   if (count == 0) return FTAR_SUCCESS;
   for (int j = 0; j < k; ++j)
     if (!srcs[j]) return FTAR_ERR_INVALID_ARG;
+  if (dt == FTAR_FLOAT8_E4M3 || dt == FTAR_FLOAT8_E5M2)  // every fp8 fold: reduce_f8.hip
+    return launch_reduce_f8(srcs, k, dst, count, dt, op, s, round_each, shape, nlevels, lds, scale);
   // a scaled k = 1 is a scaled copy through the runtime-k kernel; a plain one is a copy
   if (scale) return float_sum<true>(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale);
   if (k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)
@@ -211,6 +215,7 @@ ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t co
   case FTAR_SUM:
     switch (dt) {
       case FTAR_FLOAT32: case FTAR_FLOAT64: case FTAR_BFLOAT16: case FTAR_FLOAT16: break;  // float_sum above
+      case FTAR_FLOAT8_E4M3: case FTAR_FLOAT8_E5M2: break;  // launch_reduce_f8 above
       case FTAR_UINT8: case FTAR_INT8: e = tr<U8Sum, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_UINT16: case FTAR_INT16: e = tr<U16Sum, 8>(lds, srcs, k, dst, count, s); break;
       case FTAR_INT32: e = tr<U32Sum, 8>(lds, srcs, k, dst, count, s); break;

@@ -156,6 +156,10 @@ class RcclTransport final : public Transport {
       case FTAR_FLOAT64: t = ncclFloat64; break;
       case FTAR_BFLOAT16: t = ncclBfloat16; break;
       case FTAR_FLOAT16: t = ncclFloat16; break;
+#if defined(RCCL_FLOAT8) && RCCL_FLOAT8  // RCCL's own fp8 conversion: it may saturate where ftar's overflows
+      case FTAR_FLOAT8_E4M3: t = ncclFloat8e4m3; break;
+      case FTAR_FLOAT8_E5M2: t = ncclFloat8e5m2; break;
+#endif
       default: return FTAR_ERR_UNSUPPORTED;
     }
     ncclRedOp_t o;

@@ -40,12 +40,12 @@ _lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
 
 # ---- enums (include/ftar.h) -------------------------------------------------
 DTYPE = {"u8": 0, "i8": 1, "u16": 2, "i16": 3, "i32": 4, "i64": 5, "f32": 6, "f64": 7, "bool": 8, "bf16": 9,
-         "f16": 10}
+         "f16": 10, "f8e4m3": 12, "f8e5m2": 13}   # 11 is unassigned (ftar.h)
 # MPI names used by the reference (mpi_mod.hpp:1365-1375)
 MPI_DTYPE = {"MPI_UINT8_T": 0, "MPI_INT8_T": 1, "MPI_UINT16_T": 2, "MPI_INT16_T": 3, "MPI_INT32_T": 4,
              "MPI_INT64_T": 5, "MPI_LONG_LONG": 5, "MPI_LONG_LONG_INT": 5, "MPI_FLOAT": 6, "MPI_DOUBLE": 7,
              "MPI_C_BOOL": 8}
-# "max" / "min" (and "f16" above) are ftar extensions: the MPI names stay the reference's list
+# "max" / "min" (and "f16", "f8e4m3", "f8e5m2" above) are ftar extensions: the MPI names stay the reference's list
 OP = {"sum": 0, "band": 1, "max": 2, "min": 3, "avg": 4, "MPI_SUM": 0, "MPI_BAND": 1}  # avg: no MPI_ alias
 ALLGATHER = {"stages": 0, "collective": 1, "direct": 2}   # ftar_allgather_t
 _AG_NAME = {v: k for k, v in ALLGATHER.items()}
@@ -59,7 +59,8 @@ MAX_K = 64          # FTAR_MAX_K (ftar.h): sources of one reduce, segments of on
 _TORCH_DTYPE_NAMES = {"torch.float32": "f32", "torch.float64": "f64", "torch.bfloat16": "bf16", "torch.float16": "f16",
                       "torch.int32": "i32",
                       "torch.int64": "i64", "torch.int16": "i16", "torch.int8": "i8", "torch.uint8": "u8",
-                      "torch.bool": "bool", "torch.uint16": "u16"}
+                      "torch.bool": "bool", "torch.uint16": "u16",
+                      "torch.float8_e4m3fn": "f8e4m3", "torch.float8_e5m2": "f8e5m2"}   # the OCP formats, not fnuz
 
 
 class FtarError(RuntimeError):
@@ -215,7 +216,7 @@ _bench_lib = None
 
 def bench_lib():
     """libftar_bench.so: the A/B kernel variants (ftar_debug_reduce_variant, ftar_debug_reduce_nested_lds) and
-    kernel test hooks (ftar_debug_bf16_cvt_check, ftar_debug_f16_cvt_check) that tools/kbench*.py and the tests load; kept out of the
+    kernel test hooks (ftar_debug_bf16_cvt_check, ftar_debug_f16_cvt_check, ftar_debug_f8_cvt_check) that tools/kbench*.py and the tests load; kept out of the
     product library, which holds only the kernels the engine dispatches."""
     global _bench_lib
     if _bench_lib is None:
@@ -318,7 +319,7 @@ def last_kernel():
 def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None, scale=None):
     """dst[i] = srcs[0][i] op srcs[1][i] op ... (left to right), enqueued on `stream`.
     shape=[w0, w1, ...]: nested fold of the sources in depth-first leaf order (ftar_reduce_nested).
-    scale=s (op "sum" of f32, f64, bf16, f16): the fold's accumulator times s before its one rounding
+    scale=s (op "sum" of f32, f64, bf16, f16, f8e4m3, f8e5m2): the fold's accumulator times s before its one rounding
     (ftar_reduce_scaled: the root fold of an AVG AllReduce, s = 1 / P)."""
     arr = (_vp * len(srcs))(*[_ptr(s) for s in srcs])
     if scale is not None:

@@ -53,7 +53,10 @@ typedef enum {
   FTAR_FLOAT64 = 7, /* MPI_DOUBLE */
   FTAR_BOOL = 8,    /* MPI_C_BOOL: sum of bools == logical OR */
   FTAR_BFLOAT16 = 9, /* extension: fp32 accumulate, one RNE rounding per reduce */
-  FTAR_FLOAT16 = 10  /* extension: IEEE binary16, bf16's rules (see below) */
+  FTAR_FLOAT16 = 10, /* extension: IEEE binary16, bf16's rules (see below) */
+  /* 11 is unassigned and stays invalid: ftar_dtype_size(11) == 0 and every entry point refuses it */
+  FTAR_FLOAT8_E4M3 = 12, /* extension: OCP e4m3fn (bias 7, no inf, NaN = 0x7f / 0xff, max 448), see below */
+  FTAR_FLOAT8_E5M2 = 13  /* extension: OCP e5m2 (bias 15, IEEE-like, max 57344), see below */
 } ftar_dtype_t;
 
 typedef enum {
@@ -61,7 +64,7 @@ typedef enum {
   FTAR_BAND = 1, /* MPI_BAND (integer types only, as in the reference) */
   FTAR_MAX = 2,  /* extension: every dtype but FTAR_BOOL (see below) */
   FTAR_MIN = 3,  /* extension: every dtype but FTAR_BOOL */
-  FTAR_AVG = 4   /* extension: the mean, f32 f64 bf16 f16, the AllReduce entry points only (see below) */
+  FTAR_AVG = 4   /* extension: the mean, f32 f64 bf16 f16 f8e4m3 f8e5m2, the AllReduce entry points only (see below) */
 } ftar_op_t;
 
 /* Which (dtype, op) pairs run; the rest return FTAR_ERR_UNSUPPORTED before any device work.
@@ -71,6 +74,7 @@ typedef enum {
  *   i32 i64         x     x      x     x     -
  *   f32 f64         x     -      x     x     x     (AVG: ftar_allreduce, _group, _host, _host_group;
  *   bf16 f16        x     -      x     x     x      ftar_reduce / ftar_reduce_nested refuse it)
+ *   f8e4m3 f8e5m2   x     -      x     x     x
  *   bool            x(OR) -      -     -     -     (MPI defines no MAX/MIN on logical types either)
  *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
@@ -79,24 +83,38 @@ typedef enum {
  * in the subnormal range (gradual underflow), and reads subnormal inputs exactly.  A lane is NaN exactly
  * where that fold has a NaN; which NaN is not specified.
  *
+ * The two OCP fp8 formats (FTAR_FLOAT8_E4M3 = torch.float8_e4m3fn, FTAR_FLOAT8_E5M2 = torch.float8_e5m2; not
+ * MI300X's fnuz encodings) follow the same rules with the same rounding points: a SUM accumulates in fp32,
+ * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
+ * ring, once per node of a multi-stage tree and of ftar_reduce_nested.  Widening is exact, subnormal inputs are
+ * read exactly and results in the subnormal range are kept.  The rounding is torch's float32 -> float8 cast:
+ * RNE on the encoding, the mantissa carry running into the next encoding, and no saturation.  e5m2 overflows
+ * to +-inf at |A| >= 61440 (a tie that goes to the even encoding, inf's).  e4m3 has no inf encoding, so its
+ * overflow rounds to NaN: |A| <= 464 rounds to at most 448 (464 is a tie and 448's mantissa is even), anything
+ * above (an inf included) gives NaN.  That is deliberate: an overflow stays visible to the
+ * caller, as fp16's inf does, where a saturated 448 would be silent.  So a lane is NaN where its fold has a
+ * NaN, an inf - inf, or (e4m3 only) a rounding that overflows; which NaN pattern comes out is unspecified.
+ * RCCL's fp8 conversion may saturate instead, so ftar_rccl_allreduce (the yardstick) can differ there.
+ *
  * MAX / MIN: integers compare by the dtype's signedness (the first place u8/i8 and u16/i16 differ; SUM and
  * BAND treat them alike).  Floats follow IEEE 754-2019 maximum / minimum: -0 < +0, subnormals are not
  * flushed, a non-NaN result is bit for bit one of the sources, and any NaN source makes the lane NaN
- * (payload unspecified).  Both are exact, associative and commutative, so every topology, form, piece size
- * and buffer kind gives the same bits, and a nested shape (ftar_reduce_nested) has no effect on them.
+ * (payload unspecified); the fp8 formats alike (e5m2's infs are ordinary values, e4m3 has none).  Both are
+ * exact, associative and commutative, so every topology, form, piece size and buffer kind gives the same
+ * bits, and a nested shape (ftar_reduce_nested) has no effect on them.
  *
  * AVG (ncclAvg, torch's ReduceOp.AVG) is SUM's schedule, unchanged, except at the root fold of each block:
  * the one reduce that produces the block's final value on the rank that owns it after the reduce-scatter.
  * That fold finishes as out = round_to_dtype(A x r): A is its accumulator before its rounding (fp32 for
- * bf16 / f16, the dtype itself for f32 / f64) and r = 1.0f / (float)P (f64: 1.0 / (double)P) -- one
+ * bf16 / f16 / fp8, the dtype itself for f32 / f64) and r = 1.0f / (float)P (f64: 1.0 / (double)P) -- one
  * multiply by the reciprocal (as NCCL and torch's scalar division on the GPU do; not a division), correctly
- * rounded in the accumulator's precision, subnormal products kept; for the 16-bit floats the root's single
- * round to nearest even follows.  Inner nodes and earlier hops round exactly as under SUM; P = 1 is SUM's
+ * rounded in the accumulator's precision, subnormal products kept; for the 16-bit and 8-bit floats the root's
+ * single round to nearest even follows.  Inner nodes and earlier hops round exactly as under SUM; P = 1 is SUM's
  * copy; a lane with a NaN or an inf - inf stays NaN (payload unspecified).  For one topology every form
  * (stages, direct, collective all-gather, peer read, peer write), piece size and buffer kind gives the same
- * bits.  In the one-round forms a 16-bit mean is therefore summed in fp32, scaled and rounded once: an fp16
- * mean stays finite where the fp16 sum is inf.  The staged forms round partial sums between hops, where a
- * partial sum can still overflow.  Integers and bool return FTAR_ERR_UNSUPPORTED before any device work.
+ * bits.  In the one-round forms a 16-bit or 8-bit mean is therefore summed in fp32, scaled and rounded once: an
+ * fp16 mean stays finite where the fp16 sum is inf, an e4m3 mean where the e4m3 sum is NaN.  The staged forms
+ * round partial sums between hops, where a partial sum can still overflow.  Integers and bool return FTAR_ERR_UNSUPPORTED before any device work.
  * A one-device reduce has no P: ftar_reduce and ftar_reduce_nested refuse FTAR_AVG (FTAR_ERR_UNSUPPORTED,
  * before touching a pointer); the one-device surface is ftar_reduce_scaled.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
@@ -146,16 +164,16 @@ ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t coun
  * the k sources are the leaves, in depth-first order, of a mixed-radix tree
  * with bottom-up widths shape[0..nlevels) (product == k, nlevels <= 4).  Level
  * 0 folds shape[0] consecutive leaves, level 1 folds shape[1] consecutive
- * level-0 results, ... each node left to right; bf16 and fp16 inner nodes
+ * level-0 results, ... each node left to right; bf16, fp16 and fp8 inner nodes
  * are rounded to their format (what a staged tree stores between its stages).
  * Integer sums, AND, MAX and MIN are associative: the result equals
  * ftar_reduce's (the flat kernel runs).  nlevels <= 1 is ftar_reduce.  dst
  * may be the same address as any one source, as for ftar_reduce. */
 ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  ftar_op_t op, const int* shape, int nlevels, void* stream);
-/* Scaled SUM (extension; AVG's root fold on one device) of f32, f64, bf16 or f16: flat for nlevels <= 1,
+/* Scaled SUM (extension; AVG's root fold on one device) of f32, f64, bf16, f16 or fp8: flat for nlevels <= 1,
  * nested as ftar_reduce_nested otherwise, finishing as dst = round_to_dtype(A x scale) -- A the fold's
- * accumulator before its one rounding (fp32 for bf16 / f16; a nested fold's root, its inner nodes rounded
+ * accumulator before its one rounding (fp32 for bf16 / f16 / fp8; a nested fold's root, its inner nodes rounded
  * as ever), scale cast to float unless the dtype is f64, one correctly rounded multiply, subnormal products
  * kept.  k == 1 is a scaled copy; dst may be the same address as any one source (partial overlap is
  * undefined).  A non-finite scale returns FTAR_ERR_INVALID_ARG,
@@ -360,7 +378,7 @@ ftar_status_t ftar_comm_get_allgather(ftar_comm_t comm, ftar_allgather_t* mode);
  *   FTAR_RS_STAGES  the reference's P-1 neighbour steps (one xGMI link per rank)
  *   FTAR_RS_DIRECT  rank b-1 gathers every rank's block b in ONE round over all
  *                   links and folds them in that order with one k=P reduce
- *                   (bf16, fp16: rounded after every add, i.e. once per hop, as staged)
+ *                   (bf16, fp16, fp8: rounded after every add, i.e. once per hop, as staged)
  * Identical results.  Multi-stage trees without lonely ranks (at most 4
  * stages) likewise: FTAR_RS_DIRECT gathers the P copies of block r on rank r
  * in one round and folds them as the tree would (ftar_reduce_nested), bit for
@@ -464,8 +482,10 @@ ftar_status_t ftar_comm_get_host_chunk_bytes(ftar_comm_t comm, size_t* bytes);
  * vendor library, reduction inside RCCL): the yardstick bench.py reports next
  * to ftar at N > 1.  FTAR_ERR_UNSUPPORTED on local (in-process) groups, for
  * the types RCCL lacks (u16, i16, bool) and for BAND.  SUM, MAX, MIN and AVG map to
- * ncclSum / ncclMax / ncclMin / ncclAvg, fp16 to ncclFloat16: the arithmetic is RCCL's,
- * so its NaN and signed-zero rules for max / min, and where it rounds a mean, may differ from ftar's. */
+ * ncclSum / ncclMax / ncclMin / ncclAvg, fp16 to ncclFloat16, the fp8 formats to ncclFloat8e4m3 / ncclFloat8e5m2
+ * (an RCCL built without them: FTAR_ERR_UNSUPPORTED): the arithmetic is RCCL's, so its NaN and signed-zero rules
+ * for max / min, where it rounds a mean, and what its fp8 conversion does on overflow (it may saturate) may
+ * differ from ftar's. */
 ftar_status_t ftar_rccl_allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dtype, ftar_op_t op,
                                   ftar_comm_t comm, void* stream);
 /* xGMI calibration (collective; every rank calls it): GB/s seen by this rank

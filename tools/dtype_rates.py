@@ -4,8 +4,13 @@
 interleaved rounds, with the slowest and fastest round next to it (the run's own spread: the margin when
 one (dtype, op) is judged against another of the same width).  --op takes a list; pairs the library
 refuses (band on floats, max on bool) are skipped.  "scaled" is ftar_reduce_scaled (the sum times 1 / k before
-its rounding: AVG's root fold), to be read against "sum" of the same dtype and k in the same run.
-python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f16,f64,i32,i16,u8,bool] [--op sum,max,min,scaled]"""
+its rounding: AVG's root fold), to be read against "sum" of the same dtype and k in the same run.  A dtype may
+be named twice as "u8,u8#2": the same measurement under a label of its own, interleaved with the rest -- the
+tool's own spread between two runs of one kernel, the margin for a comparison across dtypes (the fp8 folds
+against the u8 SUM, the lightest fold of their element width; random bytes, so fp8 lanes hold NaN and inf too:
+the instructions do not care).
+python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f16,f64,i32,i16,u8,u8#2,f8e4m3,f8e5m2,bool]
+                            [--op sum,max,min,scaled]"""
 import argparse
 import json
 import os
@@ -33,7 +38,8 @@ res = {}
 ops = a.op.split(",")
 refused = set()
 for _ in range(a.rounds):
-    for d, op in ((d, op) for d in a.dtypes.split(",") for op in ops):
+    for label, op in ((d, op) for d in a.dtypes.split(",") for op in ops):
+        d = label.split("#")[0]
         n = NB // ftar.dtype_size(d)
         for k in ks:
             def launch(i):
@@ -42,7 +48,7 @@ for _ in range(a.rounds):
                     ftar.reduce(s[:k], s[max(ks)], n, d, "sum", stream=stream, scale=1.0 / k)
                 else:
                     ftar.reduce(s[:k], s[max(ks)], n, d, op, stream=stream)
-            if (d, op) in refused:
+            if (label, op) in refused:
                 continue
             try:
                 for i in range(S):
@@ -50,7 +56,7 @@ for _ in range(a.rounds):
             except ftar.FtarError as e:
                 if e.status != 2:   # "unsupported": not a pair of this library
                     raise
-                refused.add((d, op))
+                refused.add((label, op))
                 continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(stream)
@@ -58,7 +64,7 @@ for _ in range(a.rounds):
                 launch(i)
             e1.record(stream)
             torch.cuda.synchronize()
-            res.setdefault((d, op, k), []).append(e0.elapsed_time(e1) / a.reps)
+            res.setdefault((label, op, k), []).append(e0.elapsed_time(e1) / a.reps)
 for (d, op, k), ts in res.items():
     med = statistics.median(ts)
 

@@ -50,9 +50,12 @@ variants = [int(v) for v in a.variants.split(",")]
 S = max(setss)
 K = max(ks)
 bufs = [[torch.rand(n, device="cuda") for _ in range(K + 1)] for _ in range(S)]  # K sources + dst per set
-ESZ = {"f32": 4, "bf16": 2, "bf16hop": 2, "f64": 8}   # f64: nested folds only (--shapes)
-# dtype code of ftar_debug_reduce_variant for the ring's bf16 hop fold (rounds after every add; variant 62)
-CODE = {"bf16hop": ftar.DTYPE["bf16"] + 100}
+ESZ = {"f32": 4, "bf16": 2, "bf16hop": 2, "f64": 8,   # f64: nested folds only (--shapes)
+       "f8e4m3": 1, "f8e4m3max": 1, "f8e4m3keymax": 1}  # variants 40-62, k = 2 and 8
+# dtype code of ftar_debug_reduce_variant for the ring's bf16 hop fold (rounds after every add; variant 62), and
+# for the two formulations of the fp8 MAX: widen / fp32 maximum / narrow (production) and integer keys on the bytes
+CODE = {"bf16hop": ftar.DTYPE["bf16"] + 100, "f8e4m3max": ftar.DTYPE["f8e4m3"] + 200,
+        "f8e4m3keymax": ftar.DTYPE["f8e4m3"] + 300}
 stream = torch.cuda.current_stream()
 res = {}
 for r in range(a.rounds):
