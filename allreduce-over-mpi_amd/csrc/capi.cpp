@@ -205,15 +205,7 @@ ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t coun
 
 ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  ftar_op_t op, const int* shape, int nlevels, void* stream) {
-  if (nlevels < 0 || nlevels > ftar::kMaxFoldLevels || (nlevels > 0 && !shape)) return FTAR_ERR_INVALID_ARG;
-  if (nlevels > 1) {  // validate the shape for every dtype (only float sums use it)
-    long long prod = 1;
-    for (int l = 0; l < nlevels; ++l) {
-      if (shape[l] < 1) return FTAR_ERR_INVALID_ARG;
-      prod *= shape[l];
-    }
-    if (prod != k) return FTAR_ERR_INVALID_ARG;
-  }
+  FTAR_RETURN_IF(ftar::check_fold_shape(shape, nlevels, k));  // for every dtype (only float sums use it)
   return ftar::launch_reduce(srcs, k, dst, count, dtype, op, static_cast<hipStream_t>(stream), false, shape,
                              nlevels);
 }
@@ -222,19 +214,29 @@ ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size
                                  double scale, const int* shape, int nlevels, void* stream) {
   if (!ftar::dtype_scalable(dtype)) return FTAR_ERR_UNSUPPORTED;
   if (!std::isfinite(scale)) return FTAR_ERR_INVALID_ARG;
-  if (nlevels < 0 || nlevels > ftar::kMaxFoldLevels || (nlevels > 0 && !shape)) return FTAR_ERR_INVALID_ARG;
-  if (nlevels > 1) {
-    long long prod = 1;
-    for (int l = 0; l < nlevels; ++l) {
-      if (shape[l] < 1) return FTAR_ERR_INVALID_ARG;
-      prod *= shape[l];
-    }
-    if (prod != k) return FTAR_ERR_INVALID_ARG;
-  }
+  FTAR_RETURN_IF(ftar::check_fold_shape(shape, nlevels, k));
   // the kernels multiply by the scale as a float (f64: as it is); the cast happens at the launch
   const double r = dtype == FTAR_FLOAT64 ? scale : (double)(float)scale;
   return ftar::launch_reduce(srcs, k, dst, count, dtype, FTAR_SUM, static_cast<hipStream_t>(stream), false, shape,
                              nlevels, true, &r);
+}
+
+// ftar_reduce_scaled and the amax of what it stored: a 4-byte memset of the word, then the one kernel, whose
+// workgroups max into it (two nodes of a captured graph).  Everything launch_reduce would refuse is
+// refused here first, so a refused call has not zeroed *amax.
+ftar_status_t ftar_reduce_amax(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
+                               double scale, const int* shape, int nlevels, float* amax, void* stream) {
+  if (!ftar::dtype_has_amax(dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!amax || (reinterpret_cast<uintptr_t>(amax) & 3) || !std::isfinite(scale)) return FTAR_ERR_INVALID_ARG;
+  if (k < 1 || k > FTAR_MAX_K || !srcs || (!dst && count)) return FTAR_ERR_INVALID_ARG;
+  FTAR_RETURN_IF(ftar::check_fold_shape(shape, nlevels, k));
+  for (int j = 0; j < k && count; ++j)
+    if (!srcs[j]) return FTAR_ERR_INVALID_ARG;
+  const double r = (double)(float)scale;
+  FTAR_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(float), static_cast<hipStream_t>(stream)));
+  if (count == 0) return FTAR_SUCCESS;
+  return ftar::launch_reduce(srcs, k, dst, count, dtype, FTAR_SUM, static_cast<hipStream_t>(stream), false, shape,
+                             nlevels, true, &r, reinterpret_cast<unsigned*>(amax));
 }
 
 // get_stages (mpi_mod.hpp:1419-1486), minus its two bugs: an unset FT_TOPO

@@ -189,6 +189,7 @@ ftar_status_t comm_setup_local(ftar_comm* c) {
   // has 4 hardware queues by default and streams beyond that share them (tools/rccl_order/queue_probe), so a
   // device-resident user keeps the comm and reduce streams on queues of their own
   FTAR_CHECK_HIP(hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming));
+  FTAR_CHECK_ALLOC(hipMalloc(reinterpret_cast<void**>(&c->amax_buf), (1 + (size_t)c->nranks) * sizeof(unsigned)));
   if (const char* pd = getenv("FTAR_PEER_DIRECT")) {
     const std::string m(pd);
     c->peer_direct = m == "write" ? FTAR_PEER_WRITE : m == "read" ? FTAR_PEER_READ
@@ -403,6 +404,7 @@ bool comm_teardown(ftar_comm* c) {
   for (auto e : c->captured_events) hip_ignore(hipEventDestroy(e));
   for (auto e : c->tev) hip_ignore(hipEventDestroy(e));
   if (c->scratch) hip_ignore(hipFree(c->scratch));
+  if (c->amax_buf) hip_ignore(hipFree(c->amax_buf));
   if (c->staging) hip_ignore(hipFree(c->staging));
   if (c->glog.host) hip_ignore(hipHostFree(c->glog.host));
   if (c->glog.dev) hip_ignore(hipFree(c->glog.dev));
@@ -583,6 +585,13 @@ ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count,
     FTAR_RETURN_IF(first_contact(c));          // 1-rank one too, which exercises the same all-gather
     c->settings_agreed = true;
   }
+  if (c->nranks == 1 && c->amax_cur) {  // an amax call: the copy becomes a k = 1 amax fold (in place without sendbuf)
+    const void* src = sendbuf ? sendbuf : recvbuf;
+    const double one = 1.0;  // AVG of one rank: r = 1
+    return count ? launch_reduce(&src, 1, recvbuf, count, dt, FTAR_SUM, stream, false, nullptr, 0, true, &one,
+                                 c->amax_cur)
+                 : FTAR_SUCCESS;
+  }
   if (c->nranks == 1) {  // mpi_mod.hpp:1739-1746
     if (sendbuf && count && host)
       FTAR_CHECK_HIP(hipMemcpyAsync(recvbuf, sendbuf, count * esz, hipMemcpyHostToHost, stream));
@@ -593,6 +602,15 @@ ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count,
 
   FTAR_RETURN_IF(resolve_call(c, topo_auto, count, esz, host != nullptr, &call));
   const Plan& plan = *call.plan;
+  if (c->amax_cur && plan.own_block) {  // an amax call: this rank's block must have its root fold, where the
+    bool root = false;                   // amax is taken -- never a silent 0
+    for (const Stage& st : plan.stages)
+      for (const ReduceItem& r : st.reduces) root |= r.root;
+    if (!root) {
+      set_error("this plan marks no root fold for the block this rank owns: no amax of it", __FILE__, __LINE__);
+      return FTAR_ERR_UNSUPPORTED;
+    }
+  }
   switch (call.path) {
     case CallPath::PeerDevice:
       FTAR_RETURN_IF(grow_events(c, 5));
@@ -637,16 +655,29 @@ bool serial_capture() {
   return on;
 }
 
-ftar_status_t allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                        const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host) {
-  if (!c) return FTAR_ERR_INVALID_ARG;
-  if (!dtype_op_supported(dt, op)) return FTAR_ERR_UNSUPPORTED;
-  if (!recvbuf) {  // MPI allows null buffers with count 0 (e.g. an empty pinned tensor): nothing to do
-    if (count) set_error("recvbuf is NULL", __FILE__, __LINE__);
-    return count ? FTAR_ERR_INVALID_ARG : FTAR_SUCCESS;
+// argument checks the C entry points share (capi.cpp, engine_api.cpp)
+ftar_status_t check_fold_shape(const int* shape, int nlevels, int k) {
+  if (nlevels < 0 || nlevels > kMaxFoldLevels || (nlevels > 0 && !shape)) return FTAR_ERR_INVALID_ARG;
+  if (nlevels > 1) {
+    long long prod = 1;
+    for (int l = 0; l < nlevels; ++l) {
+      if (shape[l] < 1) return FTAR_ERR_INVALID_ARG;
+      prod *= shape[l];
+    }
+    if (prod != k) return FTAR_ERR_INVALID_ARG;
   }
-  std::lock_guard<std::mutex> g(c->mu);
-  FTAR_CHECK_HIP(hipSetDevice(c->device));
+  return FTAR_SUCCESS;
+}
+ftar_status_t amax_supported(ftar_dtype_t dt, ftar_op_t op) {
+  if ((op == FTAR_SUM || op == FTAR_AVG) && dtype_has_amax(dt)) return FTAR_SUCCESS;
+  set_error("the amax entry points take SUM and AVG of f32, bf16, f16, f8e4m3 and f8e5m2", __FILE__, __LINE__);
+  return FTAR_ERR_UNSUPPORTED;
+}
+
+namespace {
+// one call with the communicator's lock held and its device current
+ftar_status_t allreduce_held(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                             const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host) {
   // under capture the graph's own dependencies order its replays: an event recorded outside the capture
   // is not waited on inside it, nor is the marker re-recorded by a captured call
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -678,6 +709,96 @@ ftar_status_t allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_d
     c->done_recorded = true;
   }
   return st;
+}
+}  // namespace
+
+ftar_status_t allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                        const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host) {
+  if (!c) return FTAR_ERR_INVALID_ARG;
+  if (!dtype_op_supported(dt, op)) return FTAR_ERR_UNSUPPORTED;
+  if (!recvbuf) {  // MPI allows null buffers with count 0 (e.g. an empty pinned tensor): nothing to do
+    if (count) set_error("recvbuf is NULL", __FILE__, __LINE__);
+    return count ? FTAR_ERR_INVALID_ARG : FTAR_SUCCESS;
+  }
+  std::lock_guard<std::mutex> g(c->mu);
+  FTAR_CHECK_HIP(hipSetDevice(c->device));
+  return allreduce_held(sendbuf, recvbuf, count, dt, op, topo, c, stream, host);
+}
+
+// The AllReduce and the amax of its result (ftar.h), all on `stream`: zero this rank's word; the unchanged
+// AllReduce, whose root folds max the |stored value| keys of this rank's block into it (fold_op, the amax
+// finish of reduce_impl.h); a second, P-element AllReduce of the ranks' words -- rank r's in slot r, zeros
+// elsewhere, so no block is empty -- as MAX on FTAR_INT32: the key of a non-negative float is its bit pattern, a
+// NAN's sorts above every number, and the integer MAX is exact on every topology and form; then one k = P fold
+// of the slots into the caller's word.  The execution model prices neither extra step.
+ftar_status_t allreduce_amax(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                             const ftar_topo_t* topo, ftar_comm* c, float* amax, hipStream_t stream) {
+  FTAR_RETURN_IF(amax_supported(dt, op));
+  if (!amax || (reinterpret_cast<uintptr_t>(amax) & 3) || (!recvbuf && count)) {
+    set_error(!amax ? "amax is NULL" : recvbuf ? "amax is not 4-byte aligned" : "recvbuf is NULL", __FILE__, __LINE__);
+    return FTAR_ERR_INVALID_ARG;
+  }
+  if (!c) return FTAR_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> g(c->mu);
+  FTAR_CHECK_HIP(hipSetDevice(c->device));
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  FTAR_CHECK_HIP(hipStreamIsCapturing(stream, &cs));
+  if (cs != hipStreamCaptureStatusNone) {
+    set_error("ftar_allreduce_amax does not run under stream capture yet (ftar_reduce_amax and ftar_allreduce do)",
+              __FILE__, __LINE__);
+    return FTAR_ERR_UNSUPPORTED;
+  }
+  const size_t P = (size_t)c->nranks;
+  unsigned* const word = c->amax_buf;
+  unsigned* const slots = c->amax_buf + 1;
+  if (count == 0) {  // nothing stored: +0.0
+    FTAR_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(float), stream));
+    return FTAR_SUCCESS;
+  }
+  // The word and the slots are the communicator's, like its scratch: a call on another stream than the previous
+  // call's waits for that call's completion marker before it zeroes them (allreduce_held's rule, applied before
+  // this call's first write), and the marker is recorded again below, after this call's last read of them.
+  if (c->done_recorded && c->done_stream != stream) FTAR_CHECK_HIP(hipStreamWaitEvent(stream, c->done_ev, 0));
+  auto done = [&]() -> ftar_status_t {
+    FTAR_CHECK_HIP(hipEventRecord(c->done_ev, stream));
+    c->done_stream = stream;
+    c->done_recorded = true;
+    return FTAR_SUCCESS;
+  };
+  FTAR_CHECK_HIP(hipMemsetAsync(c->amax_buf, 0, (1 + P) * sizeof(unsigned), stream));
+  c->amax_cur = word;
+  ftar_status_t st = allreduce_held(sendbuf, recvbuf, count, dt, op, topo, c, stream, nullptr);
+  c->amax_cur = nullptr;
+  if (st != FTAR_SUCCESS) {
+    (void)done();  // the memset is enqueued: a later call on another stream still orders behind it
+    return st;
+  }
+  if (P == 1) {
+    FTAR_CHECK_HIP(hipMemcpyAsync(amax, word, sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+    return done();
+  }
+  FTAR_CHECK_HIP(hipMemcpyAsync(slots + c->rank, word, sizeof(unsigned), hipMemcpyDeviceToDevice, stream));
+  // the second round is internal: ftar_comm_last_exec and the phase marks keep describing the bucket's AllReduce
+  const ftar_exec_t bucket_exec = c->last_exec;
+  const size_t bucket_marks = c->nmarks;
+  const bool timing = c->phase_timing;
+  c->phase_timing = false;
+  st = allreduce_held(nullptr, slots, P, FTAR_INT32, FTAR_MAX, topo, c, stream, nullptr);
+  c->phase_timing = timing;
+  c->nmarks = bucket_marks;
+  c->last_exec = bucket_exec;
+  if (st != FTAR_SUCCESS) {
+    (void)done();
+    return st;
+  }
+  std::vector<const void*> srcs;
+  for (size_t lo = 0; lo < P; lo += FTAR_MAX_K - 1) {  // (more ranks than one fold has sources: in turns)
+    srcs.clear();
+    if (lo) srcs.push_back(amax);
+    for (size_t j = lo; j < std::min(P, lo + FTAR_MAX_K - 1); ++j) srcs.push_back(slots + j);
+    FTAR_RETURN_IF(launch_reduce(srcs.data(), (int)srcs.size(), amax, 1, FTAR_INT32, FTAR_MAX, stream));
+  }
+  return done();
 }
 
 }  // namespace ftar

@@ -203,6 +203,11 @@ ftar_status_t ftar_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
   return ftar::allreduce(sendbuf, recvbuf, count, dtype, op, topo, comm, static_cast<hipStream_t>(stream));
 }
 
+ftar_status_t ftar_allreduce_amax(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dtype, ftar_op_t op,
+                                  const ftar_topo_t* topo, ftar_comm_t comm, float* amax, void* stream) {
+  return ftar::allreduce_amax(sendbuf, recvbuf, count, dtype, op, topo, comm, amax, static_cast<hipStream_t>(stream));
+}
+
 ftar_status_t ftar_allreduce_host(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dtype, ftar_op_t op,
                                   const ftar_topo_t* topo, ftar_comm_t comm, void* stream) {
   if (!recvbuf && count) return FTAR_ERR_INVALID_ARG;
@@ -525,8 +530,16 @@ class RankPool {
 
 ftar_status_t run_group(const void* const* sendbufs, void* const* recvbufs, size_t count, ftar_dtype_t dtype,
                         ftar_op_t op, const ftar_topo_t* topo, ftar_comm_t* comms, int nranks,
-                        void* const* streams, bool host) {
+                        void* const* streams, bool host, float* const* amaxes = nullptr, bool with_amax = false) {
   if (!recvbufs || !comms || nranks <= 0) return FTAR_ERR_INVALID_ARG;
+  if (with_amax) {  // refused alike for every rank, before any rank's thread runs
+    FTAR_RETURN_IF(ftar::amax_supported(dtype, op));
+    for (int r = 0; r < nranks; ++r)
+      if (!amaxes || !amaxes[r]) {
+        ftar::set_error("amax is NULL", __FILE__, __LINE__);
+        return FTAR_ERR_INVALID_ARG;
+      }
+  }
   std::vector<ftar_status_t> st(nranks, FTAR_SUCCESS);
   std::vector<std::string> why(nranks);
   // Capturing streams (the caller's capture stream for every rank): the ranks' threads take turns issuing
@@ -542,6 +555,12 @@ ftar_status_t run_group(const void* const* sendbufs, void* const* recvbufs, size
   // from the capture makes HIP's hipStreamEndCapture recurse without end at every P probed, 7.0 and 7.2 alike,
   // even when ftar funnels the ranks onto one of those streams (tools/capture/depth_probe.sh,
   // profiles/r04/capture_depth_probe.log): refused here rather than crashing the caller at its end of capture.
+  if (capturing && with_amax) {
+    ftar::set_error("ftar_allreduce_amax_group does not run under stream capture yet (ftar_reduce_amax and "
+                    "ftar_allreduce_group do)",
+                    __FILE__, __LINE__);
+    return FTAR_ERR_UNSUPPORTED;
+  }
   if (capturing)
     for (int r = 1; r < nranks; ++r)
       if (streams[r] != streams[0]) {
@@ -554,8 +573,9 @@ ftar_status_t run_group(const void* const* sendbufs, void* const* recvbufs, size
     hipStream_t s = streams ? static_cast<hipStream_t>(streams[r]) : nullptr;
     const void* sb = sendbufs ? sendbufs[r] : nullptr;
     if (capturing) comms[r]->tp->capture_enter();
-    st[r] = host ? ftar_allreduce_host(sb, recvbufs[r], count, dtype, op, topo, comms[r], s)
-                 : ftar::allreduce(sb, recvbufs[r], count, dtype, op, topo, comms[r], s);
+    st[r] = host        ? ftar_allreduce_host(sb, recvbufs[r], count, dtype, op, topo, comms[r], s)
+            : with_amax ? ftar::allreduce_amax(sb, recvbufs[r], count, dtype, op, topo, comms[r], amaxes[r], s)
+                        : ftar::allreduce(sb, recvbufs[r], count, dtype, op, topo, comms[r], s);
     if (capturing) comms[r]->tp->capture_leave();
     // device buffers: the call returns once every rank's work is enqueued on its stream (stream order, as
     // ftar_allreduce and RCCL's group calls); host buffers: once they hold the result
@@ -599,6 +619,12 @@ ftar_status_t ftar_allreduce_group(const void* const* sendbufs, void* const* rec
                                    ftar_dtype_t dtype, ftar_op_t op, const ftar_topo_t* topo, ftar_comm_t* comms,
                                    int nranks, void* const* streams) {
   return run_group(sendbufs, recvbufs, count, dtype, op, topo, comms, nranks, streams, false);
+}
+
+ftar_status_t ftar_allreduce_amax_group(const void* const* sendbufs, void* const* recvbufs, size_t count,
+                                        ftar_dtype_t dtype, ftar_op_t op, const ftar_topo_t* topo, ftar_comm_t* comms,
+                                        int nranks, float* const* amaxes, void* const* streams) {
+  return run_group(sendbufs, recvbufs, count, dtype, op, topo, comms, nranks, streams, false, amaxes, true);
 }
 
 ftar_status_t ftar_allreduce_host_group(const void* const* sendbufs, void* const* recvbufs, size_t count,

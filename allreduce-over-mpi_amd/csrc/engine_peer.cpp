@@ -125,7 +125,7 @@ ftar_status_t ensure_xbuf(ftar_comm* c, size_t bytes) {
 // the plan's fold of my block with operand i read from where(i); elements
 // [lo, lo + len) of the block only (a piece of it, host mode), dst at element lo
 ftar_status_t peer_fold(const ReduceItem& r, const Plan& plan, ftar_dtype_t dt, ftar_op_t op, void* dst,
-                        hipStream_t s, bool lds, const OperandAt& where, size_t lo, size_t len) {
+                        hipStream_t s, bool lds, const OperandAt& where, size_t lo, size_t len, unsigned* amax) {
   std::map<size_t, int> slot_peer;  // scratch slot -> the rank that would have sent it
   for (const Transfer& x : plan.stages[0].recvs) slot_peer[x.off] = x.peer;
   std::vector<const void*> srcs;
@@ -139,9 +139,10 @@ ftar_status_t peer_fold(const ReduceItem& r, const Plan& plan, ftar_dtype_t dt, 
     }
   }
   if (lo >= r.len) return FTAR_SUCCESS;
-  const FoldOp fo = fold_op(op, dt, plan.nranks);  // AVG: SUM, scaled on the root item (every piece of it)
+  // AVG: SUM, scaled on the root item (every piece of it); an amax call: the root item maxes into its word too
+  const FoldOp fo = fold_op(op, dt, plan.nranks, amax);
   return launch_reduce(srcs.data(), (int)srcs.size(), dst, std::min(len, r.len - lo), dt, fo.op, s, r.round_each,
-                       r.shape.data(), (int)r.shape.size(), lds, fo.scale(r.root));
+                       r.shape.data(), (int)r.shape.size(), lds, fo.scale(r.root), fo.amax(r.root));
 }
 
 namespace {
@@ -224,7 +225,7 @@ ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
     for (const ReduceItem& r : rs.reduces)
       FTAR_RETURN_IF(peer_fold(r, plan, dt, op, out + r.off * esz, c->comm_s, c->peer_lds, [&](int q, size_t off) -> const void* {
         return q < 0 ? in + off * esz : reg_peer(rin, in, q) + off * esz;  // that rank's input, in place
-      }));
+      }, 0, SIZE_MAX, c->amax_cur));
     FTAR_RETURN_IF(mark(c, "fold (remote reads)", c->comm_s));
     FTAR_RETURN_IF(tp->barrier(c->comm_s));
     FTAR_RETURN_IF(mark(c, "barrier", c->comm_s));
@@ -243,7 +244,7 @@ ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
     for (const ReduceItem& r : rs.reduces)
       FTAR_RETURN_IF(peer_fold(r, plan, dt, op, X + r.off * esz, c->comm_s, c->peer_lds, [&](int q, size_t off) -> const void* {
         return q < 0 ? X + off * esz : Xq[q] + off * esz;  // that rank's copy of this block
-      }));
+      }, 0, SIZE_MAX, c->amax_cur));
     FTAR_RETURN_IF(mark(c, "fold (remote reads)", c->comm_s));
     FTAR_RETURN_IF(tp->barrier(c->comm_s));
     FTAR_RETURN_IF(mark(c, "barrier", c->comm_s));
@@ -265,7 +266,7 @@ ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
     for (const ReduceItem& r : rs.reduces)
       FTAR_RETURN_IF(peer_fold(r, plan, dt, op, out + r.off * esz, c->comm_s, c->peer_lds, [&](int q, size_t off) -> const void* {
         return q < 0 ? in + off * esz : X + (size_t)q * slot_bytes;  // rank q's copy, pushed into slot q
-      }));
+      }, 0, SIZE_MAX, c->amax_cur));
     FTAR_RETURN_IF(mark(c, "fold (local)", c->comm_s));
     segs.clear();  // my final block into every peer's final area, or straight into its registered output
     for (const Transfer& x : ag.sends)

@@ -86,7 +86,8 @@ ftar_status_t staged_allreduce(const void* sendbuf, void* recvbuf, size_t count,
                                const Plan& plan, size_t model_chunk, ftar_comm* c, hipStream_t stream,
                                const HostIO* host) {
   const size_t esz = dtype_size(dt), nst = plan.stages.size();
-  const FoldOp fo = fold_op(op, dt, c->nranks);  // AVG: SUM, scaled by 1 / P on the plan's root items
+  // AVG: SUM, scaled by 1 / P on the plan's root items; an amax call: they max into the call's word too
+  const FoldOp fo = fold_op(op, dt, c->nranks, c->amax_cur);
   // Host mode: the buffers are in host memory and move through a device
   // staging buffer, piece by piece, so H2D (PCIe in), the exchange, and D2H
   // (PCIe out) run at the same time.  Every src/dst transfer and reduce of a
@@ -232,7 +233,7 @@ ftar_status_t staged_allreduce(const void* sendbuf, void* recvbuf, size_t count,
         for (const Operand& o : r.srcs) srcs.push_back(sbuf(o.buf, o.off + lo, s));
         FTAR_RETURN_IF(launch_reduce(srcs.data(), (int)srcs.size(), bufs[BUF_DST] + (r.off + lo) * esz,
                                      std::min(chunk, r.len - lo), dt, fo.op, c->red_s, r.round_each, r.shape.data(),
-                                     (int)r.shape.size(), true, fo.scale(r.root)));
+                                     (int)r.shape.size(), true, fo.scale(r.root), fo.amax(r.root)));
       }
       FTAR_CHECK_HIP(hipEventRecord(ev_r(s, k), c->red_s));
     }

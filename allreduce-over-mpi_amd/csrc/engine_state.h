@@ -121,6 +121,11 @@ struct ftar_comm {
   // host buffers on a host-bootstrapped communicator in the read form: piece-pipelined
   // (peer_allreduce_host); FTAR_HOST_PEER_PIPELINE=0 takes the whole-bucket path instead (A/B)
   bool host_peer_pipeline = true;
+  // ftar_allreduce_amax (engine.cpp allreduce_amax): 1 + nranks device words allocated at setup -- word 0 is
+  // this rank's block's amax key, maxed into by the call's root folds (amax_cur points at it for the length
+  // of that call's AllReduce, else null), words 1.. the P slots of the second, tiny AllReduce (MAX of keys)
+  unsigned* amax_buf = nullptr;
+  unsigned* amax_cur = nullptr;
   bool capturing = false;  // the current call's stream is being captured: no allocation, no host sync
   bool serial = false;     // ... and every internal stream is the caller's (serial_capture)
   // events handed to captured calls: each captured call records a fresh set
@@ -181,6 +186,9 @@ bool comm_teardown(ftar_comm* c);
 // one call on a communicator (device buffers, or host ones when `host` is set)
 ftar_status_t allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
                         const ftar_topo_t* topo, ftar_comm* c, hipStream_t stream, const HostIO* host = nullptr);
+// ... and the amax of its result in *amax (ftar_allreduce_amax; device buffers, SUM and AVG)
+ftar_status_t allreduce_amax(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,
+                             const ftar_topo_t* topo, ftar_comm* c, float* amax, hipStream_t stream);
 // the reduce stream on `cus` CUs (0 = all); refused on RCCL communicators
 ftar_status_t set_reduce_cus(ftar_comm* c, int cus);
 // the form (ftar_form_t) a reduce-scatter, an all-gather and a peer mode make, or -2 for a mix no form names;
@@ -205,7 +213,8 @@ ftar_status_t ensure_xbuf(ftar_comm* c, size_t bytes);
 using OperandAt = std::function<const void*(int, size_t)>;
 // the plan's fold of my block with its operands read from where(); elements [lo, lo + len) of the block only
 ftar_status_t peer_fold(const ReduceItem& r, const Plan& plan, ftar_dtype_t dt, ftar_op_t op, void* dst,
-                        hipStream_t s, bool lds, const OperandAt& where, size_t lo = 0, size_t len = SIZE_MAX);
+                        hipStream_t s, bool lds, const OperandAt& where, size_t lo = 0, size_t len = SIZE_MAX,
+                        unsigned* amax = nullptr);  // amax: the word the root item also maxes into (an amax call)
 // the cross-GPU copies of the peer forms: one copy-kernel launch over every segment, or DMA copies
 ftar_status_t peer_copy(ftar_comm* c, const std::vector<Segment>& segs);
 ftar_status_t peer_allreduce(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dt, ftar_op_t op,

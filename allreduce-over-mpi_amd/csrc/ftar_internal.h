@@ -139,6 +139,7 @@ struct Plan {
   int allgather = FTAR_AG_STAGES;
   int reduce_scatter = FTAR_RS_STAGES;
   size_t scratch_half = 0;  // elements per scratch half (stages alternate halves)
+  size_t own_block = 0;     // elements of the block this rank owns after the reduce-scatter (mark_root)
   int max_k = 0;
   std::string json() const;
 };
@@ -168,28 +169,47 @@ ftar_status_t check_world(const Topology& t, int nranks, size_t count, Form form
 // fold's root, inner nodes rounded as ever), r = *scale cast to float (f64: as it is); round_each folds
 // then round before each add, so the last sum reaches the multiply unrounded; k == 1 is a scaled copy.
 // op = FTAR_AVG is refused here: the engine runs it as SUM with a scale on root items (root_scale).
+// amax (only with a scale; f32, bf16, fp16, fp8, else FTAR_ERR_UNSUPPORTED): the launch also maxes the fp32
+// bits of the largest |stored value| into *amax (device memory), one no-return atomicMax per workgroup; the
+// caller zeroes the word before the first launch, and every piece of one fold passes the same word.
 constexpr int kMaxFoldLevels = 4;
 ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
                             hipStream_t stream, bool round_each = false, const int* shape = nullptr,
-                            int nlevels = 0, bool lds = true, const double* scale = nullptr);
+                            int nlevels = 0, bool lds = true, const double* scale = nullptr,
+                            unsigned* amax = nullptr);
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op);  // the AllReduce entry points' matrix (AVG included)
 bool dtype_scalable(ftar_dtype_t dt);                    // the six float dtypes
+bool dtype_has_amax(ftar_dtype_t dt);                    // ... whose amax fits a float: all but f64
+// what the amax AllReduce entry points take: SUM and AVG of those; else FTAR_ERR_UNSUPPORTED with the error set
+ftar_status_t amax_supported(ftar_dtype_t dt, ftar_op_t op);
+// ftar_reduce_nested's / _scaled's / _amax's shape argument against k: nlevels in 0..kMaxFoldLevels, and from two
+// levels on every width >= 1 with the product k; else FTAR_ERR_INVALID_ARG
+ftar_status_t check_fold_shape(const int* shape, int nlevels, int k);
+// launch_reduce's amax finish of f32, bf16 and fp16 (reduce_amax.hip, a translation unit of its own as
+// reduce_f8.hip is; fp8's amax finish is in that one); arguments already checked, k >= 1, count > 0
+ftar_status_t launch_reduce_amax(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt,
+                                 hipStream_t stream, bool round_each, const int* shape, int nlevels, bool lds,
+                                 double scale, unsigned* amax);
 // launch_reduce's fp8 half (reduce_f8.hip, a translation unit of its own: it compiles beside
 // reduce_kernels.hip); arguments already checked, k >= 1, count > 0, op one of SUM, MAX, MIN
 ftar_status_t launch_reduce_f8(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
                                hipStream_t stream, bool round_each, const int* shape, int nlevels, bool lds,
-                               const double* scale);
+                               const double* scale, unsigned* amax = nullptr);
 // AVG on the engine's folds: the op the kernels run (SUM) and the scale of item r (1 / P as a float, f64:
 // as a double, on root items; none elsewhere).  Other ops pass through.
+// amax (an amax call, ftar_allreduce_amax; SUM or AVG): root items also max into that word, SUM's with the
+// scale 1 (the amax finish is a scaled one; the multiply by 1 is exact).
 struct FoldOp {
   ftar_op_t op;
   double r;
   bool avg;
-  const double* scale(bool root) const { return avg && root ? &r : nullptr; }
+  unsigned* word = nullptr;
+  const double* scale(bool root) const { return (avg || word) && root ? &r : nullptr; }
+  unsigned* amax(bool root) const { return root ? word : nullptr; }
 };
-inline FoldOp fold_op(ftar_op_t op, ftar_dtype_t dt, int nranks) {
-  if (op != FTAR_AVG) return {op, 1.0, false};
-  return {FTAR_SUM, dt == FTAR_FLOAT64 ? 1.0 / (double)nranks : (double)(1.0f / (float)nranks), true};
+inline FoldOp fold_op(ftar_op_t op, ftar_dtype_t dt, int nranks, unsigned* amax = nullptr) {
+  if (op != FTAR_AVG) return {op, 1.0, false, amax};
+  return {FTAR_SUM, dt == FTAR_FLOAT64 ? 1.0 / (double)nranks : (double)(1.0f / (float)nranks), true, amax};
 }
 // dst_i[0..bytes_i) = src_i[0..bytes_i) for up to FTAR_MAX_K segments in one
 // launch (the peer-direct all-gather: each segment pulls one rank's block).

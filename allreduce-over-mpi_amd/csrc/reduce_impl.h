@@ -55,18 +55,21 @@ inline thread_local const void* g_last_kernel = nullptr;
     ::ftar::g_last_kernel = reinterpret_cast<const void*>(KERNEL);       \
     hipLaunchKernelGGL(KERNEL, __VA_ARGS__);                             \
   } while (0)
-// A fold family in either finish (PlainFin / ScaledFin below): NAME_kernel<TARGS>(args...) or, with SC, its
-// twin NAME_scaled_kernel<TARGS>(args..., SCALE).  TARGS is parenthesised; only the kernel launched is
-// instantiated, so traits without a scaled finish never name one.
+// A fold family in one of its finishes (PlainFin / ScaledFin / AmaxFin below), by SC (kFinPlain / kFinScaled /
+// kFinAmax): NAME_kernel<TARGS>(args...), its twin NAME_scaled_kernel<TARGS>(args..., SCALE), or
+// NAME_amax_kernel<TARGS>(args..., SCALE, AMAX).  TARGS is parenthesised; only the kernel launched is
+// instantiated, so traits without a scaled or an amax finish never name one.
 #define FTAR_TARGS(...) __VA_ARGS__
-#define FTAR_LAUNCH_FIN(SC, SCALE, NAME, TARGS, ...)                                             \
-  do {                                                                                           \
-    if constexpr (SC) FTAR_LAUNCH((NAME##_scaled_kernel<FTAR_TARGS TARGS>), __VA_ARGS__, SCALE); \
-    else FTAR_LAUNCH((NAME##_kernel<FTAR_TARGS TARGS>), __VA_ARGS__);                            \
+#define FTAR_LAUNCH_FIN(SC, SCALE, AMAX, NAME, TARGS, ...)                                                    \
+  do {                                                                                                        \
+    if constexpr ((SC) == 2) FTAR_LAUNCH((NAME##_amax_kernel<FTAR_TARGS TARGS>), __VA_ARGS__, SCALE, AMAX);   \
+    else if constexpr ((SC) == 1) FTAR_LAUNCH((NAME##_scaled_kernel<FTAR_TARGS TARGS>), __VA_ARGS__, SCALE);  \
+    else FTAR_LAUNCH((NAME##_kernel<FTAR_TARGS TARGS>), __VA_ARGS__);                                         \
   } while (0)
 
 namespace {
 
+constexpr int kFinPlain = 0, kFinScaled = 1, kFinAmax = 2;  // FTAR_LAUNCH_FIN's SC (false / true: the first two)
 constexpr int kThreads = 256;
 constexpr int kTreeLevels = kMaxFoldLevels;
 // Measured on MI355X with COLD data (tools/kbench_cold.py: launches rotate over
@@ -149,6 +152,16 @@ __device__ __forceinline__ A mul_rn(A a, R r) {
   return a * r;
 }
 
+// The amax finish's keys (AmaxFin below): |encoding| as an unsigned integer is monotone in |value| in every float
+// format here and every NAN encoding sorts above every number, so the running maximum is an integer max on
+// the stored bits -- a u32 for fp32, two u16 lanes of a dword (v_pk_max_u16) for the 16- and 8-bit formats.
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned pk_umax16(unsigned a, unsigned b) {
+  return __builtin_bit_cast(unsigned,
+                            __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
 // ---------------------------------------------------------------------------
 // element traits: scalar (S*) and 16-byte vector (V*) forms of one (dtype, op)
 // ---------------------------------------------------------------------------
@@ -169,6 +182,14 @@ struct F32Sum {
   using SC = float;  // scaled finish (ScaledFin): one multiply in the accumulator's precision
   __device__ static SA s_scale(SA a, SC r) { return mul_rn(a, r); }
   __device__ static VA v_scale(VA a, SC r) { return mul_rn(a, r); }
+  // amax finish (AmaxFin): the key of a stored vector / element, the max of two keys, a key as fp32 bits
+  __device__ static unsigned v_key(u32x4 o) {
+    const u32x4 m = o & 0x7fffffffu;
+    return umax(umax(m.x, m.y), umax(m.z, m.w));
+  }
+  __device__ static unsigned s_key(S o) { return __float_as_uint(o) & 0x7fffffffu; }
+  __device__ static unsigned key_max(unsigned a, unsigned b) { return umax(a, b); }
+  __device__ static unsigned key_f32(unsigned k) { return k; }
 };
 struct F64Sum {
   using S = double;
@@ -272,6 +293,16 @@ struct H16SumT {
     return p;
   }
   __device__ static VA v_scale(VA a, SC r) { return {mul_rn(a.lo, r), mul_rn(a.hi, r)}; }
+  // amax finish: two u16 lanes of |encoding|; the winner widens exactly (v_cvt_f32_f16, << 16)
+  __device__ static unsigned v_key(u32x4 o) {
+    const u32x4 m = o & 0x7fff7fffu;
+    return pk_umax16(pk_umax16(m.x, m.y), pk_umax16(m.z, m.w));
+  }
+  __device__ static unsigned s_key(S o) { return o & 0x7fffu; }
+  __device__ static unsigned key_max(unsigned a, unsigned b) { return pk_umax16(a, b); }
+  __device__ static unsigned key_f32(unsigned k) {
+    return __float_as_uint(F::widen((unsigned short)umax(k & 0xffffu, k >> 16)));
+  }
 };
 // folded hop by hop: every add rounds to the format (the one-round ring fold has
 // to reproduce the staged ring, which rounds once per hop)
@@ -376,6 +407,18 @@ struct F8SumT {
     return p;
   }
   __device__ static VA v_scale(VA a, SC r) { return {mul_rn(a.a, r), mul_rn(a.b, r), mul_rn(a.c, r), mul_rn(a.d, r)}; }
+  // amax finish: byte keys |b| <= 0x7f, the even and the odd bytes of a dword as two u16 lanes each (there is
+  // no packed u8 max); the winner widens exactly (v_cvt_f32_fp8 / _bf8; e4m3's 0x7f is its NAN)
+  __device__ static unsigned v_key(u32x4 o) {
+    const u32x4 e = o & 0x007f007fu, d = (o >> 8) & 0x007f007fu;
+    return pk_umax16(pk_umax16(pk_umax16(e.x, e.y), pk_umax16(e.z, e.w)),
+                     pk_umax16(pk_umax16(d.x, d.y), pk_umax16(d.z, d.w)));
+  }
+  __device__ static unsigned s_key(S o) { return o & 0x7fu; }
+  __device__ static unsigned key_max(unsigned a, unsigned b) { return pk_umax16(a, b); }
+  __device__ static unsigned key_f32(unsigned k) {
+    return __float_as_uint(F::widen((unsigned char)umax(k & 0xffffu, k >> 16)));
+  }
 };
 // the ring's one-round fold: rounded after every add (H16SumHopT), or, under a scaled finish, before each add
 // (H16SumHopPreT)
@@ -585,14 +628,22 @@ struct F8KeyMinMax {
   }
 };
 
-// The finish of a fold: how the accumulator becomes the stored value.  One *_body per kernel family, two finishes:
+// The finish of a fold: how the accumulator becomes the stored value.  One *_body per kernel family, three finishes:
 //   PlainFin: the trait's own v_fin / s_fin (every op and dtype);
 //   ScaledFin (AVG's root fold, ftar_reduce_scaled; the float sums): out = round_to_dtype(A * r), one multiply
 //     in the accumulator's precision (fp32 for bf16 / fp16; subnormal products kept), then the fold's single
 //     rounding.  A nested fold hands it the root unrounded (kRawRoot, tree_push).
-// A family's two __global__ kernels, NAME_kernel(args) and NAME_scaled_kernel(args, scale), are two-line
-// wrappers over its body: profiles and tools key on those names and argument lists.  (The register kernels
-// reduce_vec_kernel and reduce_tree_kernel are the exception, see there: only their scaled kernel has a body.)
+//   AmaxFin (ftar_reduce_amax, the root folds of ftar_allreduce_amax; f32, bf16, fp16, fp8): ScaledFin's value
+//     (SUM passes r = 1: the multiply is exact), and a per-lane running maximum of the stored values'
+//     |encoding| (the traits' keys).  When the body ends, flush() widens each lane's winner to fp32 bits
+//     (the bit pattern of a non-negative float is its own key), maxes them over the wave (__shfl_xor) and over
+//     the workgroup's waves (one LDS word each), and one lane issues ONE no-return agent-scope atomicMax on
+//     the caller's word: zeroed before the first launch, it holds the answer once the last launch has ended.
+//     The state and the flush exist only under `if constexpr (kIsAmax<Fin>)`: the other kernels are unchanged.
+// A family's __global__ kernels, NAME_kernel(args), NAME_scaled_kernel(args, scale) and NAME_amax_kernel(args,
+// scale, unsigned* amax), are two-line wrappers over its body: profiles and tools key on those names and
+// argument lists.  (The register kernels reduce_vec_kernel and reduce_tree_kernel are the exception, see there:
+// their plain kernel is a copy of the body's loop.)
 template <class Tr>
 struct PlainFin {
   static constexpr bool kRawRoot = false;
@@ -606,6 +657,56 @@ struct ScaledFin {
   __device__ typename Tr::S s(typename Tr::SA a) const { return Tr::s_fin(Tr::s_scale(a, r)); }
   __device__ u32x4 v(typename Tr::VA a) const { return Tr::v_fin(Tr::v_scale(a, r)); }
 };
+template <class Tr>
+struct AmaxFin {
+  static constexpr bool kRawRoot = true;
+  typename Tr::SC r;
+  unsigned* word;
+  unsigned key = 0;
+  __device__ typename Tr::S s(typename Tr::SA a) {
+    const typename Tr::S o = Tr::s_fin(Tr::s_scale(a, r));
+    key = Tr::key_max(key, Tr::s_key(o));
+    return o;
+  }
+  __device__ u32x4 v(typename Tr::VA a) {
+    const u32x4 o = Tr::v_fin(Tr::v_scale(a, r));
+    key = Tr::key_max(key, Tr::v_key(o));
+    return o;
+  }
+  // every lane of the workgroup, once, after its last store; wave w's word is slots[w * stride] (LDS)
+  __device__ void flush(unsigned* slots, unsigned stride) {
+    unsigned m = Tr::key_f32(key);
+#pragma unroll
+    for (int o = 32; o; o >>= 1) m = umax(m, (unsigned)__shfl_xor((int)m, o));
+    const unsigned nw = blockDim.x >> 6;
+    if ((threadIdx.x & 63) == 0) slots[(threadIdx.x >> 6) * stride] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (unsigned w = 1; w < nw; ++w) m = umax(m, slots[w * stride]);
+      // One address takes about 88 atomics per microsecond, returning or not: a launch of 131,072 two-wave
+      // workgroups (f32 k = 2 on 256 MiB) spent 1.5 ms in them against 0.12 ms of memory traffic.
+      // The word only grows while a call runs, so a workgroup whose maximum is not above what it reads there
+      // (an L2 read, which one address serves far faster) has nothing to add: after the first few workgroups
+      // nearly all of them skip the atomic.  A value read stale is smaller, and only costs an atomic.  The
+      // read sits here, last: issued before the reduction the 2-byte k = 2 launch took 0.148 ms against 0.137
+      // (profiles/amax/).
+      if (m > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        (void)__hip_atomic_fetch_max(word, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+};
+template <class Fin>
+constexpr bool kIsAmax = false;
+template <class Tr>
+constexpr bool kIsAmax<AmaxFin<Tr>> = true;
+// the flush of a kernel that stages nothing through LDS: one word per wave of its own
+template <class Fin>
+__device__ __forceinline__ void amax_flush(Fin& fin) {
+  if constexpr (kIsAmax<Fin>) {
+    __shared__ unsigned slots[16];
+    fin.flush(slots, 1);
+  }
+}
 
 template <int K>
 struct Srcs {
@@ -690,9 +791,9 @@ __global__ void __launch_bounds__(BS)
 // the compiler optimises the body before it inlines it into the kernel and hoists every kernarg pointer load
 // to the kernel's entry: the static-K instantiations (the A/B variants of bench_kernels.hip) came out
 // different, a dozen of them with more VGPRs and an occupancy step lost (tools/asm_diff.py, profiles/README.md).
-template <class Tr, int K, int U, bool NTL, bool NTS, int BS>
+template <class Tr, int K, int U, bool NTL, bool NTS, int BS, class Fin>
 __device__ __forceinline__ void reduce_vec_body(const Srcs<(K > 0 ? K : FTAR_MAX_K)>& src, int kr, void* dst,
-                                                size_t nvec, int head, int tail, ScaledFin<Tr> fin) {
+                                                size_t nvec, int head, int tail, Fin fin) {
   using S = typename Tr::S;
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
   const int k = K > 0 ? K : kr;
@@ -749,6 +850,7 @@ __device__ __forceinline__ void reduce_vec_body(const Srcs<(K > 0 ? K : FTAR_MAX
       a = Tr::v_comb(a, ld16<NTL>(reinterpret_cast<const u32x4*>(static_cast<const S*>(src.p[j]) + head) + v));
     st16<NTS>(d + v, fin.v(a));
   }
+  amax_flush(fin);
 }
 
 template <class Tr, int K, int U, bool NTL, bool NTS, int BS = kThreads>
@@ -756,6 +858,12 @@ __global__ void __launch_bounds__(BS)
     reduce_vec_scaled_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, void* dst, size_t nvec, int head,
                              int tail, typename Tr::SC scale) {
   reduce_vec_body<Tr, K, U, NTL, NTS, BS>(src, kr, dst, nvec, head, tail, ScaledFin<Tr>{scale});
+}
+template <class Tr, int K, int U, bool NTL, bool NTS, int BS = kThreads>
+__global__ void __launch_bounds__(BS)
+    reduce_vec_amax_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, void* dst, size_t nvec, int head,
+                           int tail, typename Tr::SC scale, unsigned* amax) {
+  reduce_vec_body<Tr, K, U, NTL, NTS, BS>(src, kr, dst, nvec, head, tail, AmaxFin<Tr>{scale, amax});
 }
 
 // LDS-staged reduce: the production kernel for k = 2..16 (launch_k; A/B
@@ -782,9 +890,13 @@ __device__ __forceinline__ void wait_vmcnt() {
 // combines the K values get(0..K-1) of one 16-B vector slot (get(j) = source
 // j's vector, from LDS or, on the partial tile, from memory), `elem(e)` folds
 // element e alone (unaligned head / short tail, workgroup 0).
+// Returns the staging LDS (wave w's region starts kLdsWaveWords<K, U> words after wave w - 1's): the amax
+// finish leaves each wave's word in its own region once the wave has read its last tile back.
+template <int K, int U>
+constexpr unsigned kLdsWaveWords = U * K * 64 * 4;
 template <class Tr, int K, int U, int W, int AUX, bool PROG, class Fold, class Elem>
-__device__ __forceinline__ void lds_staged(const Srcs<K>& src, void* dst, size_t nvec, int head, int tail, Fold fold,
-                                           Elem elem) {
+__device__ __forceinline__ unsigned* lds_staged(const Srcs<K>& src, void* dst, size_t nvec, int head, int tail,
+                                                Fold fold, Elem elem) {
   static_assert(W * U * K <= 160, "LDS per workgroup = W x U x K KiB <= 160 KiB");
   using S = typename Tr::S;
   constexpr int VE = 16 / sizeof(S);
@@ -822,13 +934,14 @@ __device__ __forceinline__ void lds_staged(const Srcs<K>& src, void* dst, size_t
       st16<kNtStores>(d + v, fold([&](int j) { return ld16<kNtLoads>(sp(j) + v); }));
     }
   }
+  return reinterpret_cast<unsigned*>(&lds[0][0][0][0]);
 }
 
 template <class Tr, int K, int U, int W, int AUX, bool PROG, class Fin>
 __device__ __forceinline__ void reduce_lds_body(const Srcs<K>& src, void* dst, size_t nvec, int head, int tail,
                                                 Fin fin) {
   using S = typename Tr::S;
-  lds_staged<Tr, K, U, W, AUX, PROG>(
+  unsigned* const lds = lds_staged<Tr, K, U, W, AUX, PROG>(
       src, dst, nvec, head, tail,
       [&](auto get) {
         typename Tr::VA a = Tr::v_init(get(0));
@@ -841,6 +954,8 @@ __device__ __forceinline__ void reduce_lds_body(const Srcs<K>& src, void* dst, s
         for (int j = 1; j < K; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
         return fin.s(a);
       });
+  if constexpr (kIsAmax<Fin>) fin.flush(lds, kLdsWaveWords<K, U>);
+  else (void)lds;
 }
 template <class Tr, int K, int U, int W, int AUX, bool PROG>
 __global__ void __launch_bounds__(W * 64)
@@ -852,17 +967,23 @@ __global__ void __launch_bounds__(W * 64)
     reduce_lds_scaled_kernel(Srcs<K> src, void* dst, size_t nvec, int head, int tail, typename Tr::SC scale) {
   reduce_lds_body<Tr, K, U, W, AUX, PROG>(src, dst, nvec, head, tail, ScaledFin<Tr>{scale});
 }
+template <class Tr, int K, int U, int W, int AUX, bool PROG>
+__global__ void __launch_bounds__(W * 64)
+    reduce_lds_amax_kernel(Srcs<K> src, void* dst, size_t nvec, int head, int tail, typename Tr::SC scale,
+                           unsigned* amax) {
+  reduce_lds_body<Tr, K, U, W, AUX, PROG>(src, dst, nvec, head, tail, AmaxFin<Tr>{scale, amax});
+}
 
-template <class Tr, int K, int U, int W = 4, int AUX = 2, bool PROG = true, bool SC = false>
+template <class Tr, int K, int U, int W = 4, int AUX = 2, bool PROG = true, int SC = kFinPlain>
 hipError_t launch_lds(const void* const* srcs, void* dst, size_t nvec, hipStream_t s, int head = 0, int tail = 0,
-                      double r = 1.0) {
+                      double r = 1.0, unsigned* am = nullptr) {
   if constexpr (W * U * K > 160) {
     return hipErrorInvalidValue;
   } else {
     const size_t per_block = (size_t)W * U * 64;
     const size_t blocks = (nvec + per_block - 1) / per_block;
     const dim3 grid((unsigned)(blocks ? blocks : 1));
-    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_lds, (Tr, K, U, W, AUX, PROG), grid, dim3(W * 64), 0, s,
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_lds, (Tr, K, U, W, AUX, PROG), grid, dim3(W * 64), 0, s,
                     pack_srcs<K>(srcs, K), dst, nvec, head, tail);
     return hipGetLastError();
   }
@@ -878,6 +999,7 @@ __device__ __forceinline__ void reduce_elem_body(const Srcs<FTAR_MAX_K>& src, in
     for (int j = 1; j < k; ++j) a = Tr::s_comb(a, static_cast<const S*>(src.p[j])[e]);
     static_cast<S*>(dst)[e] = fin.s(a);
   }
+  amax_flush(fin);
 }
 template <class Tr>
 __global__ void __launch_bounds__(kThreads)
@@ -888,6 +1010,11 @@ template <class Tr>
 __global__ void __launch_bounds__(kThreads)
     reduce_elem_scaled_kernel(Srcs<FTAR_MAX_K> src, int k, void* dst, size_t n, typename Tr::SC scale) {
   reduce_elem_body<Tr>(src, k, dst, n, ScaledFin<Tr>{scale});
+}
+template <class Tr>
+__global__ void __launch_bounds__(kThreads)
+    reduce_elem_amax_kernel(Srcs<FTAR_MAX_K> src, int k, void* dst, size_t n, typename Tr::SC scale, unsigned* amax) {
+  reduce_elem_body<Tr>(src, k, dst, n, AmaxFin<Tr>{scale, amax});
 }
 
 // ---------------------------------------------------------------------------
@@ -978,13 +1105,13 @@ __device__ __forceinline__ void tree_push(typename O::A (&acc)[kTreeLevels][U], 
 
 template <class Tr, class Fin>
 __device__ __forceinline__ typename Tr::S tree_elem(const void* const* p, int k, const TreeCode& tc, size_t e,
-                                                    Fin fin) {
+                                                    Fin&& fin) {  // by reference: the amax finish keeps state
   using S = typename Tr::S;
   using O = TreeOps<Tr, false>;
   typename O::A acc[kTreeLevels][1], v[1];
   for (int j = 0; j < k; ++j) {
     v[0] = Tr::s_init(static_cast<const S*>(p[j])[e]);
-    tree_push<Fin::kRawRoot, O, 1>(acc, v, tc.c[j], j == k - 1);
+    tree_push<std::remove_reference_t<Fin>::kRawRoot, O, 1>(acc, v, tc.c[j], j == k - 1);
   }
   return fin.s(v[0]);
 }
@@ -1103,12 +1230,19 @@ __device__ __forceinline__ void reduce_tree_body(const Srcs<(K > 0 ? K : FTAR_MA
     }
     d[vi] = fin.v(v[0]);
   }
+  amax_flush(fin);
 }
 template <class Tr, int K, int U, class Sh = RuntimeShape>
 __global__ void __launch_bounds__(kThreads)
     reduce_tree_scaled_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, TreeCode tc, void* dst, size_t nvec,
                               int head, int tail, typename Tr::SC scale) {
   reduce_tree_body<Tr, K, U, Sh>(src, kr, tc, dst, nvec, head, tail, ScaledFin<Tr>{scale});
+}
+template <class Tr, int K, int U, class Sh = RuntimeShape>
+__global__ void __launch_bounds__(kThreads)
+    reduce_tree_amax_kernel(Srcs<(K > 0 ? K : FTAR_MAX_K)> src, int kr, TreeCode tc, void* dst, size_t nvec,
+                            int head, int tail, typename Tr::SC scale, unsigned* amax) {
+  reduce_tree_body<Tr, K, U, Sh>(src, kr, tc, dst, nvec, head, tail, AmaxFin<Tr>{scale, amax});
 }
 
 // element-wise, for sources not co-aligned with dst
@@ -1119,6 +1253,7 @@ __device__ __forceinline__ void reduce_tree_elem_body(const Srcs<FTAR_MAX_K>& sr
   const size_t stride = (size_t)gridDim.x * kThreads;
   for (size_t e = (size_t)blockIdx.x * kThreads + threadIdx.x; e < n; e += stride)
     static_cast<S*>(dst)[e] = tree_elem<Tr>(src.p, k, tc, e, fin);
+  amax_flush(fin);
 }
 template <class Tr>
 __global__ void __launch_bounds__(kThreads)
@@ -1131,6 +1266,12 @@ __global__ void __launch_bounds__(kThreads)
                                    typename Tr::SC scale) {
   reduce_tree_elem_body<Tr>(src, k, tc, dst, n, ScaledFin<Tr>{scale});
 }
+template <class Tr>
+__global__ void __launch_bounds__(kThreads)
+    reduce_tree_elem_amax_kernel(Srcs<FTAR_MAX_K> src, int k, TreeCode tc, void* dst, size_t n,
+                                 typename Tr::SC scale, unsigned* amax) {
+  reduce_tree_elem_body<Tr>(src, k, tc, dst, n, AmaxFin<Tr>{scale, amax});
+}
 
 // The nested fold on the LDS-staged tile loop (lds_staged): the production
 // path for the multi-stage trees' one-round reduce-scatter up to 16 ranks.
@@ -1140,7 +1281,7 @@ template <class Tr, int K, int U, int W, class Sh, class Fin>
 __device__ __forceinline__ void reduce_tree_lds_body(const Srcs<K>& src, const TreeCode& tc, void* dst, size_t nvec,
                                                      int head, int tail, Fin fin) {
   using O = TreeOps<Tr, true>;
-  lds_staged<Tr, K, U, W, 2, true>(
+  unsigned* const lds = lds_staged<Tr, K, U, W, 2, true>(
       src, dst, nvec, head, tail,
       [&](auto get) {
         typename O::A acc[kTreeLevels][1], v[1];
@@ -1153,6 +1294,8 @@ __device__ __forceinline__ void reduce_tree_lds_body(const Srcs<K>& src, const T
         return fin.v(v[0]);
       },
       [&](size_t e) { return tree_elem<Tr>(src.p, K, tc, e, fin); });
+  if constexpr (kIsAmax<Fin>) fin.flush(lds, kLdsWaveWords<K, U>);
+  else (void)lds;
 }
 template <class Tr, int K, int U, int W, class Sh>
 __global__ void __launch_bounds__(W * 64)
@@ -1164,6 +1307,12 @@ __global__ void __launch_bounds__(W * 64)
     reduce_tree_lds_scaled_kernel(Srcs<K> src, TreeCode tc, void* dst, size_t nvec, int head, int tail,
                                   typename Tr::SC scale) {
   reduce_tree_lds_body<Tr, K, U, W, Sh>(src, tc, dst, nvec, head, tail, ScaledFin<Tr>{scale});
+}
+template <class Tr, int K, int U, int W, class Sh>
+__global__ void __launch_bounds__(W * 64)
+    reduce_tree_lds_amax_kernel(Srcs<K> src, TreeCode tc, void* dst, size_t nvec, int head, int tail,
+                                typename Tr::SC scale, unsigned* amax) {
+  reduce_tree_lds_body<Tr, K, U, W, Sh>(src, tc, dst, nvec, head, tail, AmaxFin<Tr>{scale, amax});
 }
 
 // ---------------------------------------------------------------------------
@@ -1270,27 +1419,32 @@ inline Split16 split16(const void* const* srcs, int k, const void* dst, size_t c
 // grid of the element-wise kernels: grid-stride beyond 8192 workgroups
 inline unsigned elem_blocks(size_t count) { return (unsigned)std::min<size_t>((count + kThreads - 1) / kThreads, 8192); }
 
-template <class Tr, int K, int U, bool NTL, bool NTS, int BS, bool SC = false>
+template <class Tr, int K, int U, bool NTL, bool NTS, int BS, int SC = kFinPlain>
 hipError_t launch_cfg(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
-                      size_t max_blocks, double r = 1.0) {
+                      size_t max_blocks, double r = 1.0, unsigned* am = nullptr) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
   const size_t per_block = (size_t)U * BS;
   size_t blocks = (nvec + per_block - 1) / per_block;
   if (blocks == 0) blocks = 1;  // head/tail only
   if (max_blocks && blocks > max_blocks) blocks = max_blocks;  // grid-stride over the rest
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_vec, (Tr, K, U, NTL, NTS, BS), dim3((unsigned)blocks), dim3(BS), 0, s,
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_vec, (Tr, K, U, NTL, NTS, BS), dim3((unsigned)blocks), dim3(BS), 0, s,
                   pack_srcs<KK>(srcs, k), k, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
-template <class Tr, int K, bool SC = false>
+template <class Tr, int K, int SC = kFinPlain>
 hipError_t launch_k(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
-                    double r = 1.0) {
+                    double r = 1.0, unsigned* am = nullptr) {
+  // the amax finish ends every workgroup with a reduction and one L2 read: the 4-byte k = 2 shape of two-wave,
+  // one-tile workgroups (131,072 of them on 256 MiB) pays it eight times as often as 4 x 4, the 2-byte shape
+  constexpr bool kWide = SC == kFinAmax && K == 2 && sizeof(typename Tr::S) >= 4;
   if constexpr (K >= 2)
-    return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 2, true, SC>(srcs, dst, nvec, s, head, tail, r);
+    return launch_lds<Tr, K, (kWide ? 4 : kLdsTiles<Tr, K>), (kWide ? 4 : kLdsWaves<Tr, K>), 2, true, SC>(
+        srcs, dst, nvec, s, head, tail, r, am);
   else
-    return launch_cfg<Tr, K, kUnroll, kNtLoads, kNtStores, kVecThreads, SC>(srcs, k, dst, nvec, head, tail, s, 0, r);
+    return launch_cfg<Tr, K, kUnroll, kNtLoads, kNtStores, kVecThreads, SC>(srcs, k, dst, nvec, head, tail, s, 0, r,
+                                                                            am);
 }
 
 // Leaf codes of a nested fold with bottom-up widths shape[0..nlevels) over k
@@ -1307,36 +1461,36 @@ bool make_tree_code(const int* shape, int nlevels, int k, TreeCode* tc) {
   return true;
 }
 
-template <class Tr, int K, int U, class Sh = RuntimeShape, bool SC = false>
+template <class Tr, int K, int U, class Sh = RuntimeShape, int SC = kFinPlain>
 hipError_t launch_tree_k(const void* const* srcs, int k, const TreeCode& tc, void* dst, size_t nvec, int head,
-                         int tail, hipStream_t s, double r = 1.0) {
+                         int tail, hipStream_t s, double r = 1.0, unsigned* am = nullptr) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
   size_t blocks = (nvec + (size_t)U * kThreads - 1) / ((size_t)U * kThreads);
   if (blocks == 0) blocks = 1;
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_tree, (Tr, K, U, Sh), dim3((unsigned)blocks), dim3(kThreads), 0, s,
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_tree, (Tr, K, U, Sh), dim3((unsigned)blocks), dim3(kThreads), 0, s,
                   pack_srcs<KK>(srcs, k), k, tc, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
-template <class Tr, int K, class Sh = RuntimeShape, bool SC = false>
+template <class Tr, int K, class Sh = RuntimeShape, int SC = kFinPlain>
 hipError_t launch_tree_lds(const void* const* srcs, const TreeCode& tc, void* dst, size_t nvec, int head, int tail,
-                           hipStream_t s, double r = 1.0) {
+                           hipStream_t s, double r = 1.0, unsigned* am = nullptr) {
   constexpr int U = kLdsTiles<Tr, K>, W = kLdsWaves<Tr, K>;
   const size_t per_block = (size_t)W * U * 64;
   const size_t blocks = (nvec + per_block - 1) / per_block;
-  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_tree_lds, (Tr, K, U, W, Sh), dim3((unsigned)(blocks ? blocks : 1)),
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_tree_lds, (Tr, K, U, W, Sh), dim3((unsigned)(blocks ? blocks : 1)),
                   dim3(W * 64), 0, s, pack_srcs<K>(srcs, K), tc, dst, nvec, head, tail);
   return hipGetLastError();
 }
 
-template <class Tr, bool SC = false>
+template <class Tr, int SC = kFinPlain>
 hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const int* shape, int nlevels, void* dst,
-                       size_t count, hipStream_t s, bool lds, double r = 1.0) {
+                       size_t count, hipStream_t s, bool lds, double r = 1.0, unsigned* am = nullptr) {
   using S = typename Tr::S;
   const Split16 sp = split16(srcs, k, dst, count, sizeof(S));
   if (!sp.co_aligned) {
-    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_tree_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_tree_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
                     pack_srcs<FTAR_MAX_K>(srcs, k), k, tc, dst, count);
     return hipGetLastError();
   }
@@ -1352,51 +1506,52 @@ hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const
   // v_cvt_pk_bf16_f32 (kLdsDeepBf16) on (2,2,2) and (2,2,2,2) too; its
   // runtime-coded folds still lose there and keep the register kernel.
   if (lds) {
-    if (is({2, 2})) return launch_tree_lds<Tr, 4, StaticShape<2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-    if (is({2, 4})) return launch_tree_lds<Tr, 8, StaticShape<2, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-    if (is({4, 2})) return launch_tree_lds<Tr, 8, StaticShape<4, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-    if (is({4, 4})) return launch_tree_lds<Tr, 16, StaticShape<4, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+    if (is({2, 2})) return launch_tree_lds<Tr, 4, StaticShape<2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    if (is({2, 4})) return launch_tree_lds<Tr, 8, StaticShape<2, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    if (is({4, 2})) return launch_tree_lds<Tr, 8, StaticShape<4, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    if (is({4, 4})) return launch_tree_lds<Tr, 16, StaticShape<4, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
   }
   if (lds && (sizeof(S) >= 4 || kLdsDeepBf16)) {
-    if (is({2, 2, 2})) return launch_tree_lds<Tr, 8, StaticShape<2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-    if (is({2, 2, 2, 2})) return launch_tree_lds<Tr, 16, StaticShape<2, 2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+    if (is({2, 2, 2})) return launch_tree_lds<Tr, 8, StaticShape<2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    if (is({2, 2, 2, 2})) return launch_tree_lds<Tr, 16, StaticShape<2, 2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
   }
   if (lds && sizeof(S) >= 4) {
     switch (k) {  // other shapes: runtime leaf codes
-      case 4: return launch_tree_lds<Tr, 4, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-      case 6: return launch_tree_lds<Tr, 6, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-      case 8: return launch_tree_lds<Tr, 8, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-      case 9: return launch_tree_lds<Tr, 9, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-      case 12: return launch_tree_lds<Tr, 12, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
-      case 16: return launch_tree_lds<Tr, 16, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r);
+      case 4: return launch_tree_lds<Tr, 4, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+      case 6: return launch_tree_lds<Tr, 6, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+      case 8: return launch_tree_lds<Tr, 8, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+      case 9: return launch_tree_lds<Tr, 9, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+      case 12: return launch_tree_lds<Tr, 12, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+      case 16: return launch_tree_lds<Tr, 16, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
       default: break;
     }
-    return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+    return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
   }
   // registers (round 1; the A/B reference of ftar_debug_reduce_nested_lds)
-  if (is({2, 2})) return launch_tree_k<Tr, 4, 2, StaticShape<2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-  if (is({2, 4})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-  if (is({4, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<4, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-  if (is({2, 2, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-  if (is({4, 4})) return launch_tree_k<Tr, 16, 1, StaticShape<4, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-  if (is({2, 2, 2, 2})) return launch_tree_k<Tr, 16, 1, StaticShape<2, 2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+  if (is({2, 2})) return launch_tree_k<Tr, 4, 2, StaticShape<2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+  if (is({2, 4})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+  if (is({4, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<4, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+  if (is({2, 2, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+  if (is({4, 4})) return launch_tree_k<Tr, 16, 1, StaticShape<4, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+  if (is({2, 2, 2, 2})) return launch_tree_k<Tr, 16, 1, StaticShape<2, 2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
   switch (k) {  // other shapes: runtime leaf codes; 16 sources fit one vector per lane
-    case 4: return launch_tree_k<Tr, 4, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-    case 6: return launch_tree_k<Tr, 6, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-    case 8: return launch_tree_k<Tr, 8, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-    case 16: return launch_tree_k<Tr, 16, 1, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
-    default: return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r);
+    case 4: return launch_tree_k<Tr, 4, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+    case 6: return launch_tree_k<Tr, 6, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+    case 8: return launch_tree_k<Tr, 8, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+    case 16: return launch_tree_k<Tr, 16, 1, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+    default: return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
   }
 }
 
 // HOT: the largest k with an unrolled LDS-staged kernel (fp32/bf16/fp16 16, the other types, fp8 included, 8; 0 = k = 2
 // only); larger k take the runtime-k register kernel.  The other types gained 4-6 % at k = 8 on the
 // LDS kernel (tools/dtype_rates.py, profiles/r02/s4/dtype_rates*.log).
-template <class Tr, int HOT, bool SC = false>
-hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0) {
+template <class Tr, int HOT, int SC = kFinPlain>
+hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0,
+                     unsigned* am = nullptr) {
   const Split16 sp = split16(srcs, k, dst, count, sizeof(typename Tr::S));
   if (!sp.co_aligned) {
-    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, reduce_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
                     pack_srcs<FTAR_MAX_K>(srcs, k), k, dst, count);
     return hipGetLastError();
   }
@@ -1405,13 +1560,13 @@ hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hi
   [&]<int... I>(std::integer_sequence<int, I...>) {  // k = 2 .. max(2, HOT), unrolled
     ((k == I + 2 && (I + 2 == 2 || I + 2 <= HOT)
           ? (e = launch_k<Tr, (I + 2 <= (HOT > 2 ? HOT : 2) ? I + 2 : 2), SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail,
-                                                                              s, r),
+                                                                              s, r, am),
              done = true)
           : false),
      ...);
   }(std::make_integer_sequence<int, (HOT > 2 ? HOT : 2) - 1>{});
   if (done) return e;
-  return launch_k<Tr, 0, SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail, s, r);
+  return launch_k<Tr, 0, SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail, s, r, am);
 }
 
 }  // namespace

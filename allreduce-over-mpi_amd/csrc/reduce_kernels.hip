@@ -25,6 +25,8 @@ bool dtype_scalable(ftar_dtype_t dt) {
          dt == FTAR_FLOAT8_E4M3 || dt == FTAR_FLOAT8_E5M2;
 }
 
+bool dtype_has_amax(ftar_dtype_t dt) { return dtype_scalable(dt) && dt != FTAR_FLOAT64; }
+
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op) {
   if (dtype_size(dt) == 0) return false;
   switch (op) {
@@ -195,15 +197,18 @@ ftar_status_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t 
 
 ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
                             hipStream_t s, bool round_each, const int* shape, int nlevels, bool lds,
-                            const double* scale) {
+                            const double* scale, unsigned* amax) {
   if (k < 1 || k > FTAR_MAX_K || !srcs || !dst) return FTAR_ERR_INVALID_ARG;
   if (op == FTAR_AVG || !dtype_op_supported(dt, op)) return FTAR_ERR_UNSUPPORTED;  // AVG: the engine's SUM + scale
   if (scale && (op != FTAR_SUM || !dtype_scalable(dt))) return FTAR_ERR_UNSUPPORTED;
+  if (amax && (!scale || !dtype_has_amax(dt))) return FTAR_ERR_UNSUPPORTED;
   if (count == 0) return FTAR_SUCCESS;
   for (int j = 0; j < k; ++j)
     if (!srcs[j]) return FTAR_ERR_INVALID_ARG;
   if (dt == FTAR_FLOAT8_E4M3 || dt == FTAR_FLOAT8_E5M2)  // every fp8 fold: reduce_f8.hip
-    return launch_reduce_f8(srcs, k, dst, count, dt, op, s, round_each, shape, nlevels, lds, scale);
+    return launch_reduce_f8(srcs, k, dst, count, dt, op, s, round_each, shape, nlevels, lds, scale, amax);
+  if (amax)  // the amax finish of f32, bf16 and fp16: reduce_amax.hip
+    return launch_reduce_amax(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale, amax);
   // a scaled k = 1 is a scaled copy through the runtime-k kernel; a plain one is a copy
   if (scale) return float_sum<true>(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale);
   if (k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)

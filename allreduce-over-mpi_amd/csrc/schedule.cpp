@@ -418,6 +418,7 @@ Stage direct_tree_stage(const Topology& t, size_t P, size_t me, size_t count) {
 void mark_root(Plan* p, bool ring) {
   const size_t P = (size_t)p->nranks, me = (size_t)p->rank;
   const Range mine = block_range(ring ? (me + 1) % P : me, P, p->count);
+  p->own_block = mine.len;
   if (!mine.len) return;
   ReduceItem* last = nullptr;
   for (Stage& st : p->stages)

@@ -127,6 +127,8 @@ _lib.ftar_reduce.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, _int, _v
 _lib.ftar_reduce_nested.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, _int, ctypes.POINTER(_int), _int, _vp]
 _lib.ftar_reduce_scaled.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, ctypes.c_double, ctypes.POINTER(_int),
                                     _int, _vp]
+_lib.ftar_reduce_amax.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, ctypes.c_double, ctypes.POINTER(_int),
+                                  _int, _vp, _vp]
 _lib.ftar_topo_parse.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _int, ctypes.POINTER(Topo)]
 _lib.ftar_topo_from_env.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
 _lib.ftar_topo_choose.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
@@ -157,6 +159,10 @@ _lib.ftar_comm_destroy.argtypes = [_vp]
 _lib.ftar_comm_set_chunk_bytes.argtypes = [_vp, _sz]
 _lib.ftar_comm_get_chunk_bytes.argtypes = [_vp, ctypes.POINTER(_sz)]
 _lib.ftar_allreduce.argtypes = [_vp, _vp, _sz, _int, _int, ctypes.POINTER(Topo), _vp, _vp]
+_lib.ftar_allreduce_amax.argtypes = [_vp, _vp, _sz, _int, _int, ctypes.POINTER(Topo), _vp, _vp, _vp]
+_lib.ftar_allreduce_amax_group.argtypes = [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _sz, _int, _int,
+                                           ctypes.POINTER(Topo), ctypes.POINTER(_vp), _int, ctypes.POINTER(_vp),
+                                           ctypes.POINTER(_vp)]
 _lib.ftar_rccl_allreduce.argtypes = [_vp, _vp, _sz, _int, _int, _vp, _vp]
 _lib.ftar_allreduce_group.argtypes = [ctypes.POINTER(_vp), ctypes.POINTER(_vp), _sz, _int, _int, ctypes.POINTER(Topo),
                                       ctypes.POINTER(_vp), _int, ctypes.POINTER(_vp)]
@@ -316,13 +322,21 @@ def last_kernel():
 
 
 # ---- L3: one-device reduce ----------------------------------------------------
-def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None, scale=None):
+def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None, scale=None, amax=None):
     """dst[i] = srcs[0][i] op srcs[1][i] op ... (left to right), enqueued on `stream`.
     shape=[w0, w1, ...]: nested fold of the sources in depth-first leaf order (ftar_reduce_nested).
     scale=s (op "sum" of f32, f64, bf16, f16, f8e4m3, f8e5m2): the fold's accumulator times s before its one rounding
-    (ftar_reduce_scaled: the root fold of an AVG AllReduce, s = 1 / P)."""
+    (ftar_reduce_scaled: the root fold of an AVG AllReduce, s = 1 / P).
+    amax=a device float (pointer or 1-element fp32 tensor; op "sum", not f64): also the largest |dst[i]| as stored
+    (ftar_reduce_amax); scale defaults to 1.0 then, which gives the plain sum's bits."""
     arr = (_vp * len(srcs))(*[_ptr(s) for s in srcs])
-    if scale is not None:
+    if amax is not None:
+        if _op(op) != OP["sum"]:
+            raise ValueError("amax goes with op='sum'")
+        sh = (_int * max(1, len(shape or ())))(*(shape or ()))
+        _check(_lib.ftar_reduce_amax(arr, len(srcs), _ptr(dst), count, _dt(dtype), 1.0 if scale is None else float(scale),
+                                     sh, len(shape or ()), _ptr(amax), _stream(stream)), "ftar_reduce_amax")
+    elif scale is not None:
         if _op(op) != OP["sum"]:
             raise ValueError("scale goes with op='sum'")
         sh = (_int * max(1, len(shape or ())))(*(shape or ()))
@@ -590,8 +604,15 @@ class Comm:
         _check(_lib.ftar_comm_last_exec(self.handle, ctypes.byref(e)), "last_exec")
         return e.as_dict()
 
-    def allreduce(self, sendbuf, recvbuf, count, dtype="f32", op="sum", topo_=None, lonely=0, stream=None):
+    def allreduce(self, sendbuf, recvbuf, count, dtype="f32", op="sum", topo_=None, lonely=0, stream=None, amax=None):
+        """amax=a device float (pointer or 1-element fp32 tensor): also the largest |recvbuf[i]| as stored, on
+        every rank (ftar_allreduce_amax; op "sum" / "avg" of f32, bf16, f16, f8e4m3, f8e5m2)."""
         t = None if topo_ is None else ctypes.byref(topo(topo_, lonely))
+        if amax is not None:
+            st = _lib.ftar_allreduce_amax(_ptr(sendbuf), _ptr(recvbuf), count, _dt(dtype), _op(op), t, self.handle,
+                                          _ptr(amax), _stream(stream))
+            _check(st, "ftar_allreduce_amax")
+            return
         st = _lib.ftar_allreduce(_ptr(sendbuf), _ptr(recvbuf), count, _dt(dtype), _op(op), t, self.handle,
                                  _stream(stream))
         _check(st, "ftar_allreduce")
@@ -754,18 +775,21 @@ class Comm:
         _check(_lib.ftar_comm_set_reduce_scatter(
             self.handle, REDUCE_SCATTER[mode] if isinstance(mode, str) else int(mode)), "reduce_scatter")
 
-    def allreduce_tensor(self, tensor, out=None, op="sum", topo_=None, lonely=0, stream=None):
+    def allreduce_tensor(self, tensor, out=None, op="sum", topo_=None, lonely=0, stream=None, amax=None):
         """In-place (out=None) or out-of-place AllReduce of a contiguous device tensor,
-        e.g. a data-parallel gradient bucket; dtype and count come from the tensor."""
+        e.g. a data-parallel gradient bucket; dtype and count come from the tensor.
+        amax=a 1-element fp32 tensor on the tensor's device: also the result's abs-max (Comm.allreduce)."""
+        if amax is not None and (str(amax.dtype) != "torch.float32" or amax.numel() != 1 or amax.device != tensor.device):
+            raise ValueError("amax must be a 1-element float32 tensor on the tensor's device")
         if not tensor.is_contiguous() or (out is not None and not out.is_contiguous()):
             raise ValueError("ftar needs contiguous tensors")
         if out is not None and (out.numel() != tensor.numel() or out.dtype != tensor.dtype):
             raise ValueError("out must match tensor in size and dtype")
         dt = _dt(str(tensor.dtype))
         if out is None:
-            self.allreduce(None, tensor, tensor.numel(), dt, op, topo_, lonely, stream)
+            self.allreduce(None, tensor, tensor.numel(), dt, op, topo_, lonely, stream, amax)
             return tensor
-        self.allreduce(tensor, out, tensor.numel(), dt, op, topo_, lonely, stream)
+        self.allreduce(tensor, out, tensor.numel(), dt, op, topo_, lonely, stream, amax)
         return out
 
     def rccl_allreduce(self, sendbuf, recvbuf, count, dtype="f32", op="sum", stream=None):
@@ -844,25 +868,37 @@ class LocalGroup:
             c.deregister(i)
 
     def allreduce(self, sendbufs, recvbufs, count, dtype="f32", op="sum", topo_=None, lonely=0, streams=None,
-                  host=False):
+                  host=False, amaxes=None):
         """Every rank at once, enqueued on each rank's stream (None: the NULL stream), returning once enqueued;
-        host=True: the buffers are host memory (ftar_allreduce_host_group), returning once they hold the result."""
+        host=True: the buffers are host memory (ftar_allreduce_host_group), returning once they hold the result.
+        amaxes=[one device float per rank]: also the result's abs-max on every rank (ftar_allreduce_amax_group;
+        device buffers only)."""
         P = len(self.comms)
         t = None if topo_ is None else ctypes.byref(topo(topo_, lonely))
         sb = None if sendbufs is None else (_vp * P)(*[_ptr(x) for x in sendbufs])
         rb = (_vp * P)(*[_ptr(x) for x in recvbufs])
         hs = (_vp * P)(*[c.handle for c in self.comms])
         ss = None if streams is None else (_vp * P)(*[_stream(s) for s in streams])
+        if amaxes is not None:
+            if host:
+                raise ValueError("the host-buffer calls have no amax variant")
+            if len(amaxes) != P:
+                raise ValueError("amaxes: one per rank")
+            am = (_vp * P)(*[_ptr(a) for a in amaxes])
+            _check(_lib.ftar_allreduce_amax_group(sb, rb, count, _dt(dtype), _op(op), t, hs, P, am, ss),
+                   "ftar_allreduce_amax_group")
+            return
         fn = _lib.ftar_allreduce_host_group if host else _lib.ftar_allreduce_group
         st = fn(sb, rb, count, _dt(dtype), _op(op), t, hs, P, ss)
         _check(st, "ftar_allreduce_host_group" if host else "ftar_allreduce_group")
 
-    def allreduce_tensors(self, tensors, op="sum", topo_=None, lonely=0):
-        """In-place AllReduce of one contiguous device tensor per rank (same shape and dtype)."""
+    def allreduce_tensors(self, tensors, op="sum", topo_=None, lonely=0, amaxes=None):
+        """In-place AllReduce of one contiguous device tensor per rank (same shape and dtype); amaxes=[one
+        1-element fp32 device tensor per rank]: also the result's abs-max on every rank."""
         t0 = tensors[0]
         if any(not t.is_contiguous() or t.numel() != t0.numel() or t.dtype != t0.dtype for t in tensors):
             raise ValueError("tensors must be contiguous and alike")
-        self.allreduce(None, tensors, t0.numel(), _dt(str(t0.dtype)), op, topo_, lonely)
+        self.allreduce(None, tensors, t0.numel(), _dt(str(t0.dtype)), op, topo_, lonely, amaxes=amaxes)
         return tensors
 
     def destroy(self):

@@ -77,6 +77,9 @@ typedef enum {
  *   f8e4m3 f8e5m2   x     -      x     x     x
  *   bool            x(OR) -      -     -     -     (MPI defines no MAX/MIN on logical types either)
  *
+ *   amax (ftar_reduce_amax, ftar_allreduce_amax, _amax_group): SUM and AVG of f32 bf16 f16 f8e4m3 f8e5m2;
+ *   every other dtype (f64 included: its amax does not fit the word) and every other op is refused.
+ *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
  * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
  * ring, once per node of a multi-stage tree.  For binary16 that rounding overflows to +-inf, keeps results
@@ -117,6 +120,21 @@ typedef enum {
  * round partial sums between hops, where a partial sum can still overflow.  Integers and bool return FTAR_ERR_UNSUPPORTED before any device work.
  * A one-device reduce has no P: ftar_reduce and ftar_reduce_nested refuse FTAR_AVG (FTAR_ERR_UNSUPPORTED,
  * before touching a pointer); the one-device surface is ftar_reduce_scaled.
+ *
+ * amax (the *_amax entry points): the result's abs-max, taken in the root fold of each block, where the final
+ * values sit in registers just before they are stored -- no extra pass over the bucket.  `amax` is one float
+ * in device memory on the communicator's device (ftar_reduce_amax: the current device), 4-byte aligned, written
+ * on the call's stream.  After the call it holds, on every rank, the IEEE 754-2019 maximum of |recvbuf[i]| over
+ * all `count` elements AS STORED: after the fold's one rounding, and after the 1/P multiply under AVG, widened
+ * exactly to fp32.  Any NaN element makes it a NaN (which NaN is unspecified); an inf element makes it +inf;
+ * subnormals are not flushed; all zeros (-0 included) or count == 0 give +0.0 (bits 0x00000000).  The word is
+ * overwritten, not accumulated into.  Non-NaN results are bit-identical on every rank, and for one topology
+ * across every form, piece size and buffer layout, because the result is.  SUM and AVG of f32, bf16, f16,
+ * f8e4m3 and f8e5m2; any other dtype (f64 included: its amax does not fit the word) or op returns
+ * FTAR_ERR_UNSUPPORTED, a NULL or misaligned amax FTAR_ERR_INVALID_ARG, and ftar_allreduce_amax / _amax_group
+ * under stream capture FTAR_ERR_UNSUPPORTED with a message (ftar_reduce_amax captures): every refusal comes
+ * before any device work and leaves recvbuf and *amax untouched.  The host-buffer entry points
+ * (ftar_allreduce_host, _host_group) and the MPI drop-in have no amax variant.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
@@ -180,6 +198,12 @@ ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size
  * other dtypes FTAR_ERR_UNSUPPORTED, both before any device work. */
 ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  double scale, const int* shape, int nlevels, void* stream);
+/* ftar_reduce_scaled plus the amax of what it stored (extension; the amax paragraph above): *amax = the
+ * maximum of |dst[i]| over the count elements as stored, as a float.  scale == 1.0 gives the plain SUM's bits
+ * (the multiply is exact).  f64 is refused (FTAR_ERR_UNSUPPORTED).  Enqueues a 4-byte memset of *amax and one
+ * kernel, so it captures into a HIP graph as those two nodes. */
+ftar_status_t ftar_reduce_amax(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
+                               double scale, const int* shape, int nlevels, float* amax, void* stream);
 
 /* ---- topology ------------------------------------------------------------
  * ftar_topo_parse: FT_TOPO / FT_LONELY strings (NULL = unset) for nranks.
@@ -445,6 +469,15 @@ ftar_status_t ftar_allreduce(const void* sendbuf, void* recvbuf, size_t count, f
 ftar_status_t ftar_allreduce_group(const void* const* sendbufs, void* const* recvbufs, size_t count,
                                    ftar_dtype_t dtype, ftar_op_t op, const ftar_topo_t* topo, ftar_comm_t* comms,
                                    int nranks, void* const* streams);
+/* ftar_allreduce / ftar_allreduce_group and the amax of the result (the amax paragraph at ftar_op_t above): the
+ * same AllReduce, same bits, whose root folds also keep the largest |stored value| of the block they finish; a
+ * second, internal AllReduce of one word per rank (an exact integer MAX on the fp32 bit patterns) and a 4-byte
+ * write to *amax follow on the same stream.  amaxes: one device float per rank, on that rank's device. */
+ftar_status_t ftar_allreduce_amax(const void* sendbuf, void* recvbuf, size_t count, ftar_dtype_t dtype, ftar_op_t op,
+                                  const ftar_topo_t* topo, ftar_comm_t comm, float* amax, void* stream);
+ftar_status_t ftar_allreduce_amax_group(const void* const* sendbufs, void* const* recvbufs, size_t count,
+                                        ftar_dtype_t dtype, ftar_op_t op, const ftar_topo_t* topo, ftar_comm_t* comms,
+                                        int nranks, float* const* amaxes, void* const* streams);
 
 /* ---- AllReduce of HOST buffers (the reference's own setting) ---------------
  * Replaces MPI_Allreduce_FT's host-memory contract (mpi_mod.hpp:1723-1778).

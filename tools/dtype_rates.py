@@ -4,13 +4,15 @@
 interleaved rounds, with the slowest and fastest round next to it (the run's own spread: the margin when
 one (dtype, op) is judged against another of the same width).  --op takes a list; pairs the library
 refuses (band on floats, max on bool) are skipped.  "scaled" is ftar_reduce_scaled (the sum times 1 / k before
-its rounding: AVG's root fold), to be read against "sum" of the same dtype and k in the same run.  A dtype may
+its rounding: AVG's root fold), to be read against "sum" of the same dtype and k in the same run; "amax" is
+ftar_reduce_amax with the same scale (the scaled fold plus the abs-max of what it stores: a 4-byte memset, the
+kernel, one atomic per workgroup), to be read against "sum" and "scaled" of that run.  A dtype may
 be named twice as "u8,u8#2": the same measurement under a label of its own, interleaved with the rest -- the
 tool's own spread between two runs of one kernel, the margin for a comparison across dtypes (the fp8 folds
 against the u8 SUM, the lightest fold of their element width; random bytes, so fp8 lanes hold NaN and inf too:
 the instructions do not care).
 python tools/dtype_rates.py [--ks 2,8] [--dtypes f32,bf16,f16,f64,i32,i16,u8,u8#2,f8e4m3,f8e5m2,bool]
-                            [--op sum,max,min,scaled]"""
+                            [--op sum,max,min,scaled,amax]"""
 import argparse
 import json
 import os
@@ -25,7 +27,7 @@ import ftar  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--ks", default="2,8")
 ap.add_argument("--dtypes", default="f32,bf16,f64,i64,i32,i16,u8,bool")
-ap.add_argument("--op", default="sum", help="one op or a comma list: sum,band,max,min,scaled")
+ap.add_argument("--op", default="sum", help="one op or a comma list: sum,band,max,min,scaled,amax")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=8)
 a = ap.parse_args()
@@ -34,6 +36,7 @@ ks = [int(k) for k in a.ks.split(",")]
 S = 4
 bufs = [[torch.randint(0, 256, (NB,), dtype=torch.uint8, device="cuda") for _ in range(max(ks) + 1)] for _ in range(S)]
 stream = torch.cuda.current_stream()
+amax_word = torch.zeros(1, dtype=torch.float32, device="cuda")
 res = {}
 ops = a.op.split(",")
 refused = set()
@@ -46,6 +49,8 @@ for _ in range(a.rounds):
                 s = bufs[i % S]
                 if op == "scaled":
                     ftar.reduce(s[:k], s[max(ks)], n, d, "sum", stream=stream, scale=1.0 / k)
+                elif op == "amax":
+                    ftar.reduce(s[:k], s[max(ks)], n, d, "sum", stream=stream, scale=1.0 / k, amax=amax_word)
                 else:
                     ftar.reduce(s[:k], s[max(ks)], n, d, op, stream=stream)
             if (label, op) in refused:
