@@ -1,7 +1,7 @@
 // libftar_bench.so: the A/B harness of the reduce kernels and kernel-level test hooks, kept OUT of the
 // product library (libftar.so holds only the kernels launch_reduce / launch_tree / launch_copy /
 // launch_gather dispatch).  Not part of ftar.h; loaded by tools/kbench*.py, the bf16 conversion test and the
-// kernel-edge tests (ftar_debug_reduce_ex, ftar_debug_gather) through ftar.bench_lib().  Shape, cache-policy and dtype variants of the production kernels in
+// kernel-edge tests (ftar_debug_reduce_ex, ftar_debug_reduce_amax_ex, ftar_debug_gather) through ftar.bench_lib().  Shape, cache-policy and dtype variants of the production kernels in
 // reduce_impl.h are instantiated here from the same templates; launch_gather (variant 90) and
 // launch_reduce (the nested-fold A/B) are the product's own, linked from libftar.so.
 #include "reduce_impl.h"
@@ -175,13 +175,22 @@ extern "C" ftar_status_t ftar_debug_reduce_nested_lds(int lds, const void* const
 }
 
 // Test hooks of the kernel-edge tests (tests/kernel_edges.py): the product's own launchers with every argument
-// the engine can give them.  ftar_debug_reduce_ex is launch_reduce unchanged (round_each: the hop folds;
+// the engine can give them.  ftar_debug_reduce_ex is launch_reduce unchanged but for amax (round_each: the hop folds;
 // lds = 0: the peer forms' ":vec" dispatch and the register tree kernels; scale may be NULL).
 extern "C" ftar_status_t ftar_debug_reduce_ex(const void* const* srcs, int k, void* dst, size_t count, int dtype, int op,
                                               int round_each, const int* shape, int nlevels, int lds,
                                               const double* scale, void* stream) {
   return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, (ftar_op_t)op, static_cast<hipStream_t>(stream),
                              round_each != 0, shape, nlevels, lds != 0, scale);
+}
+// The same with an amax word: every argument goes to launch_reduce unchanged (which refuses an amax without a
+// scale).  The word is NOT zeroed here: what it holds before the launch is the caller's to decide, as it is the
+// engine's, whose pieces max into one word launch after launch.
+extern "C" ftar_status_t ftar_debug_reduce_amax_ex(const void* const* srcs, int k, void* dst, size_t count, int dtype,
+                                                   int op, int round_each, const int* shape, int nlevels, int lds,
+                                                   const double* scale, unsigned* amax, void* stream) {
+  return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, (ftar_op_t)op, static_cast<hipStream_t>(stream),
+                             round_each != 0, shape, nlevels, lds != 0, scale, amax);
 }
 
 // launch_gather on dsts[i][0..bytes[i]) = srcs[i][0..bytes[i]), i < nsegs (zero-byte segments included: the

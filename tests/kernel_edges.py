@@ -1,8 +1,9 @@
 """Helpers of the kernel-edge tests (tests/test_gpu_kernel_edges.py; self-tested on the CPU by
 tests/test_kernel_edges_cpu.py): guarded arenas whose every byte outside a call's destination is checked after
 the call, the tile geometry of a launched kernel read from its name, the element counts that sit on that
-geometry's edges, inputs and expectations from the references the suite already pins, and ctypes wrappers of the
-two hooks in libftar_bench.so (ftar_debug_reduce_ex, ftar_debug_gather).
+geometry's edges, inputs and expectations from the references the suite already pins (fp8: tests/f8_ref.py; the
+amax word: tests/amax_ref.py), staircase inputs whose result steps up at chosen lanes, and ctypes wrappers of the
+hooks in libftar_bench.so (ftar_debug_reduce_ex, ftar_debug_reduce_amax_ex, ftar_debug_gather).
 
 No GPU import at module level: torch, ftar and the oracle are loaded by the functions that need them."""
 import ctypes
@@ -116,12 +117,13 @@ Geometry = namedtuple("Geometry", "family wave_tile wg_tile lds_shape")
 
 
 def geometry(symbol):
-    """The tile geometry of a fold or copy kernel from its template id (csrc/reduce_impl.h): wg_tile = the 16-byte
-    vectors one workgroup covers per pass -- W x U x 64 for the LDS-staged families, U x BS for reduce_vec*,
-    U x 256 for reduce_tree*, 2 x 256 for gather_kernel; the element-wise kernels cover 256 ELEMENTS per
-    workgroup and pass.  lds_shape = (U, W) of an LDS-staged kernel, else None."""
+    """The tile geometry of a fold or copy kernel from its template id (csrc/reduce_impl.h; NAME_scaled_kernel and
+    NAME_amax_kernel are read as NAME_kernel, their family): wg_tile = the 16-byte vectors one workgroup covers
+    per pass -- W x U x 64 for the LDS-staged families, U x BS for reduce_vec*, U x 256 for reduce_tree*, 2 x 256
+    for gather_kernel; the element-wise kernels cover 256 ELEMENTS per workgroup and pass.  lds_shape = (U, W) of
+    an LDS-staged kernel, else None."""
     name, a = template_args(symbol)
-    family = name.replace("_scaled_kernel", "_kernel")
+    family = name.replace("_scaled_kernel", "_kernel").replace("_amax_kernel", "_kernel")
     if family == "reduce_lds_kernel":           # <Tr, K, U, W, AUX, PROG>
         u, w = int(a[2]), int(a[3])
         return Geometry(family, WAVE_TILE, w * u * WAVE_TILE, (u, w))
@@ -178,8 +180,10 @@ def head_offset(ve, head):
 
 # ---- inputs and expectations ------------------------------------------------------------------------------
 STORAGE = {"u8": np.uint8, "i8": np.int8, "u16": np.uint16, "i16": np.int16, "i32": np.int32, "i64": np.int64,
-           "f32": np.float32, "f64": np.float64, "bool": np.uint8, "bf16": np.uint16, "f16": np.uint16}
-FLOATS = ("f16", "bf16", "f32", "f64")
+           "f32": np.float32, "f64": np.float64, "bool": np.uint8, "bf16": np.uint16, "f16": np.uint16,
+           "f8e4m3": np.uint8, "f8e5m2": np.uint8}
+F8 = ("f8e4m3", "f8e5m2")
+FLOATS = ("f16", "bf16", "f32", "f64") + F8
 
 
 def esize(dt):
@@ -193,7 +197,11 @@ def _f16_bits(f32):
 
 def sources(dt, op, k, n, seed=1):
     """k sources of n elements: finite, no NaN, |x| < 1 for the floats (a 64-way fp16 sum stays finite); BAND gets
-    a shared mask ORed in; MAX / MIN of floats get lanes of +-0 facing each other and of subnormals."""
+    a shared mask ORed in; MAX / MIN of floats get lanes of +-0 facing each other and of subnormals.  fp8:
+    f8_ref.finite_sources (|x| < 2, the zero, subnormal and tie lanes in every op), k <= 17."""
+    if dt in F8:
+        import f8_ref
+        return [np.ascontiguousarray(x).copy() for x in f8_ref.finite_sources(dt, max(k, 2), n, seed)[:k]]
     import f16_minmax_ref as ref
     import ftar_inputs as fi
     base = {"f16": "f32"}.get(dt, dt)
@@ -224,6 +232,8 @@ def no_nan(dt, x):
     """The CPU-side assertion that an input or expectation holds no NaN (and, being finite inputs, no inf)."""
     if dt not in FLOATS:
         return True
+    if dt in F8:    # e4m3: 0x7f is its NaN; e5m2: 0x7c inf, above it NaN
+        return not bool(((np.ascontiguousarray(x).view(np.uint8) & 0x7F) >= (0x7F if dt == "f8e4m3" else 0x7C)).any())
     import f16_minmax_ref as ref
     u, _, emask, _ = ref.FLOATS[dt]
     b = np.ascontiguousarray(x).view(u)
@@ -268,7 +278,20 @@ def expected(dt, op, ins, shape=None, scale=None, hop=False):
     import ftar_inputs as fi
     import oracle_lib
     k = len(ins)
-    if op in ("max", "min"):
+    if dt in F8:
+        import f8_ref
+        r = None if scale is None else f8_ref.scale_of(scale)
+        if op in ("max", "min"):
+            want = f8_ref.minmax(dt, op, ins)
+        elif hop and k > 2:
+            want = f8_ref.hop_fold(dt, ins, r)
+        elif shape and k > 1:
+            want = f8_ref.nested(dt, ins, shape, r)
+        elif k == 1 and r is None:
+            want = ins[0]
+        else:
+            want = f8_ref.fold(dt, ins, r)
+    elif op in ("max", "min"):
         want = ref.minmax(dt, op, [np.ascontiguousarray(x).view(ref.storage(dt)) for x in ins])
     elif hop and k > 2:
         want = hop_fold(dt, ins, scale)
@@ -288,7 +311,58 @@ def expected(dt, op, ins, shape=None, scale=None, hop=False):
     return np.ascontiguousarray(want)
 
 
-# ---- the two hooks of libftar_bench.so --------------------------------------------------------------------
+# ---- inputs whose result's |value| is known lane by lane --------------------------------------------------
+# (first |encoding|, step) of staircase(): a normal number small enough that every level of ~50 boundaries stays
+# finite, halves exactly (scale 0.5) and keeps one encoding step between neighbouring levels
+STAIR = {"f8e4m3": (0x10, 1), "f8e5m2": (0x08, 1), "bf16": (0x3000, 8), "f16": (0x3000, 8), "f32": (0x3F000000, 4096)}
+# the slot sweeps' |encoding| E of every lane: even (so E + 1 differs from it in the lowest key bit alone) with a
+# non-zero mantissa
+SWEEP_E = {"f8e4m3": 0x34, "f8e5m2": 0x36, "bf16": 0x3F94, "f16": 0x3554, "f32": 0x3F955554}
+
+
+def one_hot(dt, k, enc, seed=1):
+    """k sources in which lane i has exactly one non-zero element, in source i % k: |encoding| enc[i] under a random
+    sign; the other sources alternate +0 and -0 there.  Any SUM fold of them (flat, hop, nested; times 1.0 or, while
+    the halves stay normal, 0.5) is exact: the result's |value| in lane i is that of enc[i] (times the scale)."""
+    import amax_ref
+    u, _, _ = amax_ref.LAYOUT[dt]
+    enc = np.asarray(enc)
+    n = enc.size
+    sign = u(1) << u(8 * np.dtype(u).itemsize - 1)
+    rng = np.random.default_rng([seed, 77, k, n])
+    i = np.arange(n)
+    val = enc.astype(u) | np.where(rng.integers(0, 2, n) == 1, sign, u(0)).astype(u)
+    xs = []
+    for j in range(k):
+        zero = np.where((i + j) % 2 == 1, sign, u(0)).astype(u)
+        xs.append(np.ascontiguousarray(np.where(i % k == j, val, zero).astype(u)))
+    return xs
+
+
+def staircase(dt, k, boundaries, length, scale=None, shape=None, hop=False, seed=1):
+    """(sources, expectation) of one_hot() inputs whose lane i holds |encoding| first + step * level(i) +
+    rand(step), level(i) = how many of `boundaries` are <= i: the result's |value| never falls back under an
+    earlier level and steps strictly up AT every boundary, so a fold of [off, b) that also takes lane b (or any
+    lane behind it) into its amax gives a larger word.
+    Asserted here, on the expectation returned, for every boundary without exception:
+    key(want[b]) > max(key(want[:b]))."""
+    import amax_ref
+    first, step = STAIR[dt]
+    bs = np.array(sorted(set(int(b) for b in boundaries)), dtype=np.int64)
+    assert bs.size and 0 <= bs[0] and bs[-1] < length, "every boundary is a lane of the sources"
+    level = np.searchsorted(bs, np.arange(length), side="right")
+    rng = np.random.default_rng([seed, 78, k, length])
+    enc = first + step * level + rng.integers(0, step, length)
+    ins = one_hot(dt, k, enc, seed)
+    want = expected(dt, "sum", ins, shape=shape, scale=scale, hop=hop)
+    keys = amax_ref.keys(dt, want).astype(np.int64)
+    before = np.maximum.accumulate(keys)
+    for b in bs:
+        assert b == 0 or keys[b] > before[b - 1], ("no strict step at boundary", dt, k, int(b), scale)
+    return ins, want
+
+
+# ---- the hooks of libftar_bench.so ------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _hooks():
     import ftar
@@ -296,19 +370,28 @@ def _hooks():
     vp, sz, i = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int
     lib.ftar_debug_reduce_ex.argtypes = [ctypes.POINTER(vp), i, vp, sz, i, i, i, ctypes.POINTER(i), i, i,
                                          ctypes.POINTER(ctypes.c_double), vp]
+    lib.ftar_debug_reduce_amax_ex.argtypes = [ctypes.POINTER(vp), i, vp, sz, i, i, i, ctypes.POINTER(i), i, i,
+                                              ctypes.POINTER(ctypes.c_double), vp, vp]
     lib.ftar_debug_gather.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(sz), i, i, sz, i, vp]
     return lib
 
 
-def reduce_ex(srcs, dst, count, dt, op="sum", round_each=False, shape=None, lds=True, scale=None):
-    """ftar::launch_reduce with every argument (ftar_debug_reduce_ex)."""
+def reduce_ex(srcs, dst, count, dt, op="sum", round_each=False, shape=None, lds=True, scale=None, amax=None):
+    """ftar::launch_reduce with every argument (ftar_debug_reduce_ex).  amax=ptr: the amax finish maxing into the
+    device word at ptr AS IT IS (ftar_debug_reduce_amax_ex: no memset; the scale defaults to 1.0)."""
     import ftar
     arr = (ctypes.c_void_p * len(srcs))(*srcs)
     sh = (ctypes.c_int * max(1, len(shape or ())))(*(shape or ()))
+    if amax is not None and scale is None:
+        scale = 1.0
     sc = None if scale is None else ctypes.byref(ctypes.c_double(
         float(scale) if dt == "f64" else float(np.float32(scale))))
-    st = _hooks().ftar_debug_reduce_ex(arr, len(srcs), dst, count, ftar.DTYPE[dt], ftar.OP[op], int(round_each), sh,
-                                       len(shape or ()), int(lds), sc, None)
+    if amax is None:
+        st = _hooks().ftar_debug_reduce_ex(arr, len(srcs), dst, count, ftar.DTYPE[dt], ftar.OP[op], int(round_each),
+                                           sh, len(shape or ()), int(lds), sc, None)
+    else:
+        st = _hooks().ftar_debug_reduce_amax_ex(arr, len(srcs), dst, count, ftar.DTYPE[dt], ftar.OP[op],
+                                                int(round_each), sh, len(shape or ()), int(lds), sc, amax, None)
     assert st == 0, (st, ftar.last_error())
 
 
@@ -323,6 +406,9 @@ def gather(srcs, dsts, nbytes, nt=True, max_wg_per_seg=0, release_system=False):
 
 
 # ---- one fold, many launches ------------------------------------------------------------------------------
+WORD_AT = 16         # the amax word's offset in its 64-byte arena
+
+
 class Fold:
     """k sources and their expectation on the device, uploaded once; launches at any element offset and count are
     pointer arithmetic into the source and destination arenas.  Source j's element i sits shifts[j] + i elements
@@ -342,6 +428,20 @@ class Fold:
         self.dst = Arena(self.n * self.esz + 16, device)
         self.want = torch.from_numpy(as_bytes(want).copy()).to(device)
         assert self.want.numel() == self.n * self.esz
+        self.want_host = np.ascontiguousarray(want).reshape(-1)      # the expectation's elements, for amax_ref
+        self.am = None
+
+    def word_ptr(self):
+        """The amax word of a launch: 4 bytes at offset WORD_AT of a guarded 64-byte arena of their own."""
+        if self.am is None:
+            self.am = Arena(64, self.want.device)
+        return self.am.ptr(WORD_AT)
+
+    def set_word(self, value):
+        """What the word holds before a launch (the test's memset)."""
+        self.word_ptr()
+        raw = np.array([value], np.uint32).view(np.uint8)
+        self.am.window(WORD_AT, WORD_AT + 4).copy_(self.src.torch.from_numpy(raw.copy()))
 
     def src_off(self, j, off):
         return j * self.row + (self.shifts[j] + off) * self.esz
@@ -351,9 +451,11 @@ class Fold:
         srcs = [self.src.ptr(self.src_off(j, off)) for j in range(self.k)]
         return srcs, (self.dst.ptr(off * self.esz) if alias is None else srcs[alias])
 
-    def verify(self, off, n, alias=None):
+    def verify(self, off, n, alias=None, word=None):
         """After a launch on [off, off + n): None, or what is wrong -- the payload against the expectation, every
-        byte around it, and every source that is not the destination.  Puts the arenas back."""
+        byte around it, and every source that is not the destination.  word (amax_ref.amax_bits of the expected
+        payload): also the amax word at word_ptr() against it (amax_ref.matches) and every byte of its arena but
+        those 4.  Puts the arenas back."""
         torch = self.src.torch
         nb = n * self.esz
         if alias is None:
@@ -375,6 +477,17 @@ class Fold:
         stray = check_untouched(other)
         if stray:
             msgs.append(("source arena: " if alias is None else "destination arena: ") + stray)
+        if word is not None:
+            import amax_ref
+            self.word_ptr()
+            got_w = int(self.am.window(WORD_AT, WORD_AT + 4).cpu().numpy().view(np.uint32)[0])
+            if not amax_ref.matches(got_w, word):
+                msgs.append(f"amax word: got 0x{got_w:08x}, want "
+                            + (word if word == amax_ref.NAN else f"0x{word:08x}"))
+            stray = check_untouched(self.am, WORD_AT, WORD_AT + 4)
+            if stray:
+                msgs.append("amax word's arena: " + stray)
+            self.am.restore(-self.am.origin, self.am.total - self.am.origin)
         if msgs:
             for a in (self.src, self.dst):
                 a.restore(-a.origin, a.total - a.origin)

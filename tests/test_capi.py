@@ -29,7 +29,7 @@ def test_kernel_variants_live_in_the_bench_library_only():
     ftar_debug_last_kernel hook bench.py ties its PMC traffic to."""
     import ftar
     moved = ("ftar_debug_reduce_variant", "ftar_debug_reduce_nested_lds", "ftar_debug_bf16_cvt_check",
-             "ftar_debug_reduce_ex", "ftar_debug_gather")
+             "ftar_debug_reduce_ex", "ftar_debug_reduce_amax_ex", "ftar_debug_gather")
     assert not [n for n in moved if hasattr(ftar.lib(), n)]
     assert all(hasattr(ftar.bench_lib(), n) for n in moved)
     assert hasattr(ftar.lib(), "ftar_debug_last_kernel")

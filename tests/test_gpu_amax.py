@@ -103,9 +103,9 @@ def test_reduce_amax_is_the_scaled_fold_and_its_abs_max(dt, k, n, mean):
 
 def tile_vectors(symbol):
     """The 16-byte vectors one workgroup of a launched *_amax_kernel covers per pass (kernel_edges.geometry
-    knows the plain and the scaled names)."""
+    reads the name)."""
     assert "_amax_kernel<" in symbol, symbol
-    return kernel_edges.geometry(symbol.replace("_amax_kernel<", "_kernel<")).wg_tile
+    return kernel_edges.geometry(symbol).wg_tile
 
 
 @pytest.mark.parametrize("k", [2, 17])

@@ -5,8 +5,10 @@ for bit, every byte of the arena outside [dst, dst + n) must still hold its posi
 source that is not the destination must be unchanged.  The counts sit on the edges of the launched kernel's own
 geometry (head + nvec x VE + tail around one wave tile, one workgroup tile and three of them), which is read from
 the kernel's name, so a retune of the (U, W) tables moves the edges and these tests follow.  Inputs are finite and
-free of NaN; expectations come from the references the suite pins elsewhere (the oracle, avg_ref, f16_minmax_ref)
-and the hop folds written out in torch, computed once per case over the longest length."""
+free of NaN; expectations come from the references the suite pins elsewhere (the oracle, avg_ref, f16_minmax_ref,
+f8_ref for the two fp8 formats) and the hop folds written out in torch, computed once per case over the longest
+length.  (tests/test_gpu_f8_edges.py holds six more fp8 cases; tests/test_gpu_amax_edges.py runs the footprint
+cases of this file under the amax finish.)"""
 import numpy as np
 import pytest
 
@@ -16,6 +18,7 @@ from test_gpu_avg import FAMILIES
 pytestmark = pytest.mark.gpu
 
 THIRD = float(np.float32(1) / np.float32(3))
+QUARTER = 0.25
 ELEMENTWISE = ("reduce_elem_kernel", "reduce_tree_elem_kernel")
 
 
@@ -47,7 +50,10 @@ def probe(launch, dt, k, shifts=None):
     return ftar.last_kernel()
 
 
-def fold_for(dt, op, k, length, shape=None, scale=None, hop=False, shifts=None):
+def fold_for(dt, op, k, length, shape=None, scale=None, hop=False, shifts=None, stair=None):
+    """stair: boundaries of kernel_edges.staircase inputs (SUM; finite at any k) in place of the ordinary ones."""
+    if stair is not None:
+        return ke.Fold(*ke.staircase(dt, k, stair, length, scale=scale, shape=shape, hop=hop), shifts=shifts)
     ins = ke.sources(dt, op, k, length)
     return ke.Fold(ins, ke.expected(dt, op, ins, shape=shape, scale=scale, hop=hop), shifts=shifts)
 
@@ -76,14 +82,16 @@ def edges_of(symbol, ve):
     return g, edges
 
 
-def run_edges(launch, dt, op, k, shape=None, scale=None, hop=False, shifts=None, check_id=None):
-    """The whole of one case: probe the kernel, take its edges, build inputs and expectation once, run."""
+def run_edges(launch, dt, op, k, shape=None, scale=None, hop=False, shifts=None, check_id=None, stair=False):
+    """The whole of one case: probe the kernel, take its edges, build inputs and expectation once, run.  stair:
+    staircase inputs that step up where each count ends."""
     symbol = probe(launch, dt, k, shifts)
     if check_id:
         check_id(symbol)
     ve = 16 // ke.esize(dt)
     g, edges = edges_of(symbol, ve)
-    fold = fold_for(dt, op, k, max(e.n for e in edges) + ve, shape, scale, hop, shifts)
+    ends = [ke.head_offset(ve, e.head) + e.n for e in edges] if stair else None
+    fold = fold_for(dt, op, k, max(e.n for e in edges) + ve, shape, scale, hop, shifts, stair=ends)
     ids = run_counts(launch, fold, edges)
     assert ids == {symbol}, "one kernel for every count with vectors"
     return g
@@ -112,6 +120,10 @@ def _family_cases():
         for k in (3, 8):    # the hop folds: plain rounds after every add, scaled before (H16SumHopPreT)
             out[f"hop_{dt}_k{k}"] = dict(dt=dt, k=k, via="ex", kw=dict(round_each=True), hop=True,
                                          want_id=(f"reduce_lds_kernel<H16SumHop", f"T<{fmt}", f", {k}, "))
+    for dt, fmt in (("f8e4m3", "T<F8Fmt<false>"), ("f8e5m2", "T<F8Fmt<true>")):
+        for k in (3, 8):    # fp8's: F8SumHopT, and F8SumHopPreT under a scaled finish (at 0.25)
+            out[f"hop_{dt}_k{k}"] = dict(dt=dt, k=k, via="ex", kw=dict(round_each=True), hop=True, scale=QUARTER,
+                                         want_id=("reduce_lds_kernel<F8SumHop", fmt, f", {k}, "))
     for dt, tr in (("f32", "F32Sum"), ("bf16", "H16SumT<Bf16Fmt<")):
         out[f"vec_ab_{dt}_k3"] = dict(dt=dt, k=3, via="ex", kw=dict(lds=False),     # the peer forms' ":vec" A/B
                                       want_id=(f"reduce_vec_kernel<{tr}", ", 0, 2, true, true, 512>"))
@@ -135,7 +147,7 @@ def _launcher(c, scale):
 @pytest.mark.parametrize("family", sorted(FAMILY_CASES))
 def test_footprint_at_the_edges_of_every_family(family, finish):
     c = FAMILY_CASES[family]
-    scale = THIRD if finish == "scaled" else None
+    scale = c.get("scale", THIRD) if finish == "scaled" else None
     want_id = c["want_id"]
     if c.get("hop") and scale is not None:      # under a scaled finish the hop fold is the Pre trait
         want_id = (want_id[0] + "Pre",) + want_id[1:]
@@ -147,13 +159,16 @@ def test_footprint_at_the_edges_of_every_family(family, finish):
 WIDTHS = ["u8", "bf16", "f32", "f64"]                       # one SUM trait per element width
 ALL_K = list(range(1, 18)) + [33, 64]
 OTHER_TRAITS = ([(dt, "sum") for dt in ("i16", "i32", "i64", "bool", "f16")] + [("u8", "band"), ("i64", "band")] +
-                [(dt, op) for dt in ("i8", "u16", "f32", "f64", "bf16", "f16") for op in ("max", "min")])
+                [(dt, op) for dt in ("i8", "u16", "f32", "f64", "bf16", "f16") + ke.F8 for op in ("max", "min")])
+F8_K = list(range(2, 18))                                   # what f8_ref.finite_sources covers: the LDS kernels up
+#                                                             to 8, the runtime-k register kernel above
+F8_STAIR_K = [33, 64]                                       # on staircase inputs, finite at any k
+SUM_CASES = [(dt, k) for dt in WIDTHS for k in ALL_K] + [(dt, k) for dt in ke.F8 for k in F8_K + F8_STAIR_K]
 
 
-@pytest.mark.parametrize("k", ALL_K)
-@pytest.mark.parametrize("dt", WIDTHS)
+@pytest.mark.parametrize("dt,k", SUM_CASES, ids=[f"{d}-{k}" for d, k in SUM_CASES])
 def test_sum_at_the_edges_of_every_k(dt, k):
-    run_edges(api(dt), dt, "sum", k)
+    run_edges(api(dt), dt, "sum", k, stair=dt in ke.F8 and k in F8_STAIR_K)
 
 
 @pytest.mark.parametrize("k", [2, 8, 9, 16, 17])
@@ -175,8 +190,10 @@ def test_the_parsed_lds_shapes_differ_across_k(dt):
 
 
 # ---- dense small sweep (independent of the name parser) ---------------------------------------------------
-@pytest.mark.parametrize("k", [2, 8])
-@pytest.mark.parametrize("dt", WIDTHS)
+DENSE = [(dt, k) for dt in WIDTHS for k in (2, 8)] + [("f8e4m3", 2), ("f8e5m2", 8)]
+
+
+@pytest.mark.parametrize("dt,k", DENSE, ids=[f"{d}-{k}" for d, k in DENSE])
 def test_dense_small_counts(dt, k):
     """Every count from 0 to two wave tiles and two vectors, at heads 0 and 1."""
     ve = 16 // ke.esize(dt)
@@ -202,10 +219,13 @@ ALIAS = {
     "elem": dict(dt="f32", k=3, shifts=[0, 1, 0]),
     "tree_lds_2x4": dict(dt="f32", k=8, shape=(2, 4)),
     "tree_reg_f64_2x2": dict(dt="f64", k=4, shape=(2, 2)),
+    "f8_lds_k8": dict(dt="f8e4m3", k=8),
+    "f8_tree_lds_2x2": dict(dt="f8e5m2", k=4, shape=(2, 2)),
 }
 ALIAS_FAMILY = {"lds_k2": "reduce_lds_kernel", "lds_k8": "reduce_lds_kernel", "vec_k17": "reduce_vec_kernel",
                 "elem": "reduce_elem_kernel", "tree_lds_2x4": "reduce_tree_lds_kernel",
-                "tree_reg_f64_2x2": "reduce_tree_kernel"}
+                "tree_reg_f64_2x2": "reduce_tree_kernel", "f8_lds_k8": "reduce_lds_kernel",
+                "f8_tree_lds_2x2": "reduce_tree_lds_kernel"}
 
 
 @pytest.mark.parametrize("finish", ["plain", "scaled"])
@@ -236,8 +256,8 @@ STRIDE_N = 8192 * 256 + 256 + 3        # past the 8192-workgroup grid: a whole s
 
 
 @pytest.mark.parametrize("dt,k,shape,scale", [("u8", 2, None, None), ("f32", 3, None, None), ("bf16", 2, None, THIRD),
-                                              ("f32", 4, (2, 2), None)],
-                         ids=["u8_k2", "f32_k3", "bf16_k2_scaled", "tree_elem_f32_2x2"])
+                                              ("f32", 4, (2, 2), None), ("f8e4m3", 2, None, None)],
+                         ids=["u8_k2", "f32_k3", "bf16_k2_scaled", "tree_elem_f32_2x2", "f8e4m3_k2"])
 def test_elementwise_grid_stride(dt, k, shape, scale):
     import ftar
     shifts = [0] * (k - 1) + [1]       # the last source misaligned against dst

@@ -42,6 +42,13 @@ IDS = [
     ("reduce_elem_kernel<F32Sum>", 256, None),
     ("reduce_tree_elem_scaled_kernel<F32Sum>", 256, None),
     ("gather_kernel<true, false>", 2 * 256, None),
+    ("reduce_lds_amax_kernel<F32Sum, 2, 4, 4, 2, true>", 4 * 4 * 64, (4, 4)),     # 4-byte k = 2 under amax: 4 x 4
+    ("reduce_lds_amax_kernel<F8SumHopPreT<F8Fmt<true>>, 8, 4, 2, 2, true>", 2 * 4 * 64, (4, 2)),
+    ("reduce_vec_amax_kernel<H16SumT<HalfFmt>, 0, 2, true, true, 512>", 2 * 512, None),
+    ("reduce_tree_lds_amax_kernel<F8SumT<F8Fmt<false>>, 4, 4, 4, StaticShape<2, 2>>", 4 * 4 * 64, (4, 4)),
+    ("reduce_tree_amax_kernel<H16SumT<Bf16Fmt<true>>, 6, 2, RuntimeShape>", 2 * 256, None),
+    ("reduce_elem_amax_kernel<F32Sum>", 256, None),
+    ("reduce_tree_elem_amax_kernel<F32Sum>", 256, None),
 ]
 
 
@@ -50,7 +57,7 @@ def test_geometry_from_a_kernel_id(symbol, wg_tile, shape):
     assert ke.tiles(symbol) == (64, wg_tile)
     g = ke.geometry(symbol)
     assert g.lds_shape == shape
-    assert g.family == symbol.split("<")[0].replace("_scaled", "")
+    assert g.family == symbol.split("<")[0].replace("_scaled", "").replace("_amax", "")
 
 
 def test_geometry_reads_the_rocprof_spelling_through_kernel_symbol():
@@ -182,3 +189,118 @@ def test_inputs_are_finite_and_expectations_come_out_without_nan():
     assert not ke.no_nan("f16", nan) and not ke.no_nan("f32", np.array([np.inf], np.float32))
     ins = ke.sources("bf16", "sum", 3, 64)
     assert not np.array_equal(ke.hop_fold("bf16", ins), ke.hop_fold("bf16", ins, 0.25))
+
+
+# ---- fp8 inputs and expectations ---------------------------------------------------------------------------
+@pytest.mark.parametrize("dt", ke.F8)
+def test_fp8_inputs_and_expectations_come_from_f8_ref(dt):
+    import f8_ref
+    assert ke.STORAGE[dt] == np.uint8 and ke.esize(dt) == 1 and dt in ke.FLOATS
+    ins = ke.sources(dt, "sum", 3, 1000)
+    assert all(np.array_equal(a, b) for a, b in zip(ins, f8_ref.finite_sources(dt, 3, 1000)))
+    assert len(ke.sources(dt, "sum", 1, 10)) == 1
+    assert all(ke.no_nan(dt, x) for x in ins)
+    assert np.array_equal(ke.expected(dt, "sum", ins), f8_ref.fold(dt, ins))
+    assert np.array_equal(ke.expected(dt, "sum", ins, scale=0.25), f8_ref.fold(dt, ins, f8_ref.scale_of(0.25)))
+    assert np.array_equal(ke.expected(dt, "sum", ins, hop=True), f8_ref.hop_fold(dt, ins))
+    assert np.array_equal(ke.expected(dt, "sum", ins, hop=True, scale=0.25),
+                          f8_ref.hop_fold(dt, ins, f8_ref.scale_of(0.25)))
+    assert not np.array_equal(ke.expected(dt, "sum", ins, hop=True), ke.expected(dt, "sum", ins))
+    four = ke.sources(dt, "sum", 4, 1000)
+    assert np.array_equal(ke.expected(dt, "sum", four, shape=(2, 2)), f8_ref.nested(dt, four, (2, 2)))
+    for op in ("max", "min"):
+        assert np.array_equal(ke.expected(dt, op, ins), f8_ref.minmax(dt, op, ins))
+    assert np.array_equal(ke.expected(dt, "sum", ins[:1]), ins[0])
+    # what no_nan refuses: the format's NaN, and e5m2's inf
+    assert not ke.no_nan(dt, np.array([0xFF], np.uint8))
+    assert ke.no_nan("f8e4m3", np.array([0x7E], np.uint8)) and ke.no_nan("f8e5m2", np.array([0x7B], np.uint8))
+    assert not ke.no_nan("f8e5m2", np.array([0x7C], np.uint8))
+
+
+# ---- the staircase -----------------------------------------------------------------------------------------
+def _ends(dt, wg_tile):
+    ve = 16 // ke.esize(dt)
+    return ve, sorted({ke.head_offset(ve, e.head) + e.n for e in ke.edge_counts(ve, wg_tile)})
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.5])
+@pytest.mark.parametrize("wg_tile", [128, 512, 1024, 2048])
+@pytest.mark.parametrize("dt", ["f16", "bf16", "f32", "f8e4m3", "f8e5m2"])
+def test_staircase_steps_up_at_every_boundary(dt, wg_tile, scale):
+    """The boundaries of edge_counts: the expectation's |value| never falls back under an earlier level, steps
+    strictly up AT every boundary (staircase() asserts that itself), and -- the opposite property -- the word of [0, b) differs from
+    the word of [0, b]: a checker fed one lane too many fails."""
+    import amax_ref
+    ve, bs = _ends(dt, wg_tile)
+    assert 40 <= len(bs) <= 45
+    ins, want = ke.staircase(dt, 3, bs, max(bs) + wg_tile * ve, scale=scale)
+    assert len(ins) == 3 and want.size == max(bs) + wg_tile * ve and ke.no_nan(dt, want)
+    keys = amax_ref.keys(dt, want).astype(np.int64)
+    assert keys.min() > 0
+    nz = np.stack([amax_ref.keys(dt, x) != 0 for x in ins])
+    assert (nz.sum(axis=0) == 1).all() and (nz.argmax(axis=0) == np.arange(want.size) % 3).all()
+    signs = np.ascontiguousarray(want).view(amax_ref.storage(dt)) != amax_ref.keys(dt, want)
+    assert 0.3 < signs.mean() < 0.7, "the sign of the non-zero value is random"
+    for b in bs:
+        assert amax_ref.amax_bits(dt, want[:b]) != amax_ref.amax_bits(dt, want[:b + 1]), b
+        assert b == 0 or keys[b:].min() > keys[:b].max()
+    assert amax_ref.amax_bits(dt, want) > amax_ref.amax_bits(dt, want[:bs[-1]])      # larger values behind the last
+
+
+def test_staircase_refuses_a_boundary_outside_the_sources_and_holds_for_a_hop_and_a_nested_fold():
+    with pytest.raises(AssertionError):
+        ke.staircase("bf16", 2, [10, 100], 100)
+    for dt in ("f16", "f8e5m2"):
+        _, bs = _ends(dt, 512)
+        ke.staircase(dt, 8, bs, max(bs) + 64, scale=0.5, hop=True)
+        ke.staircase(dt, 4, bs, max(bs) + 64, scale=1.0, shape=(2, 2))
+        ke.staircase(dt, 1, bs, max(bs) + 64, scale=0.5)
+    ke.staircase("f8e4m3", 64, [5, 70], 200)                 # finite at any k
+
+
+def test_the_slot_sweeps_field_is_even_with_a_mantissa_and_one_step_widens_apart():
+    import amax_ref
+    for dt, e in ke.SWEEP_E.items():
+        assert e % 2 == 0 and e + 1 < amax_ref.LAYOUT[dt][2]
+        assert 0 < amax_ref.widen(dt, e) < amax_ref.widen(dt, e + 1) < 0x7F800000
+        ins = ke.one_hot(dt, 3, np.full(100, e))
+        want = ke.expected(dt, "sum", ins, scale=1.0)
+        assert (amax_ref.keys(dt, want) == e).all()
+
+
+# ---- Fold.verify with an amax word -------------------------------------------------------------------------
+def test_fold_verify_with_a_word_on_the_cpu():
+    """numpy plays the launch: a right word, a wrong word, and a fifth byte written beside it."""
+    import amax_ref
+    ins, want = ke.staircase("bf16", 2, [40, 253], 301, scale=1.0)
+    f = ke.Fold(ins, want, device="cpu")
+    off, n = 3, 250
+    word = amax_ref.amax_bits("bf16", want[off:off + n])
+    assert f.word_ptr() == f.am.ptr(ke.WORD_AT) and f.word_ptr() % 4 == 0 and f.am.payload_bytes == 64
+
+    def play(w):
+        f.dst.window(off * 2, (off + n) * 2).copy_(f.want[off * 2:(off + n) * 2])
+        f.set_word(w)
+    play(word)
+    assert f.verify(off, n, word=word) is None
+    assert ke.check_untouched(f.am) is None                       # and verify put the word's arena back
+    play(word)
+    assert f.verify(off, n) is None                               # without a word the word is not looked at
+    play(amax_ref.amax_bits("bf16", want[off:off + n + 1]))       # one lane too many in the key
+    assert "amax word" in f.verify(off, n, word=word)
+    play(0)
+    assert "amax word" in f.verify(off, n, word=word)
+    play(word)
+    f.am.buf[f.am.origin + ke.WORD_AT + 4] ^= 0x5A                # a fifth byte
+    assert "amax word's arena" in f.verify(off, n, word=word)
+    play(word)
+    f.am.buf[f.am.origin + ke.WORD_AT - 1] ^= 0x5A
+    assert "amax word's arena" in f.verify(off, n, word=word)
+    play(0x7FC00000)
+    assert f.verify(off, n, word=amax_ref.NAN) is None
+    assert f.verify(0, 0) is None
+
+
+def test_reduce_ex_knows_the_amax_hook():
+    import ftar
+    assert hasattr(ftar.bench_lib(), "ftar_debug_reduce_amax_ex")
