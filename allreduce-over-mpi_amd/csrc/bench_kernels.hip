@@ -4,6 +4,7 @@
 // kernel-edge tests (ftar_debug_reduce_ex, ftar_debug_reduce_amax_ex, ftar_debug_gather) through ftar.bench_lib().  Shape, cache-policy and dtype variants of the production kernels in
 // reduce_impl.h are instantiated here from the same templates; launch_gather (variant 90) and
 // launch_reduce (the nested-fold A/B) are the product's own, linked from libftar.so.
+#include "cast_impl.h"
 #include "reduce_impl.h"
 
 namespace ftar {
@@ -539,4 +540,30 @@ extern "C" void* ftar_debug_block_stream(void* stream, double seconds) {
 // Releases a stream blocked by ftar_debug_block_stream (the 4-byte flag stays allocated).
 extern "C" void ftar_debug_unblock(void* flag) {
   if (flag) __atomic_store_n(static_cast<int*>(flag), 1, __ATOMIC_SEQ_CST);
+}
+
+// The layout candidates of the scaled cast (cast_impl.h; tools/cast_rates.py): layout 0 = each lane owns one fp8
+// vector and its wide bytes, 1 = the same with the wide side transposed through LDS, 2 = lane-contiguous wide
+// vectors with 4- / 8-byte fp8 accesses; u = fp8 vectors per lane and pass (1, 2 or 4).  No amax, no memset.
+extern "C" ftar_status_t ftar_debug_cast_variant(int layout, int u, const void* src, int src_dtype, void* dst,
+                                                 int dst_dtype, size_t count, const float* scale, void* stream) {
+  using namespace ftar;
+  if (!cast_pair_supported((ftar_dtype_t)src_dtype, (ftar_dtype_t)dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!src || !dst || !count) return FTAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipErrorInvalidValue;
+#define FTAR_CAST_VARIANT(L, U_)                                                                                  \
+  if (layout == (L) && u == (U_))                                                                                 \
+    e = launch_cast_any<U_, U_, L>(src, (ftar_dtype_t)src_dtype, dst, (ftar_dtype_t)dst_dtype, count, scale, nullptr, s);
+  FTAR_CAST_VARIANT(kLayOwn, 1)
+  FTAR_CAST_VARIANT(kLayOwn, 2)
+  FTAR_CAST_VARIANT(kLayLds, 1)
+  FTAR_CAST_VARIANT(kLayLds, 2)
+  FTAR_CAST_VARIANT(kLayWide, 1)
+  FTAR_CAST_VARIANT(kLayWide, 2)
+  FTAR_CAST_VARIANT(kLayWide, 4)
+#undef FTAR_CAST_VARIANT
+  if (e == hipErrorInvalidValue) return FTAR_ERR_INVALID_ARG;
+  FTAR_CHECK_HIP(e);
+  return FTAR_SUCCESS;
 }

@@ -239,6 +239,20 @@ ftar_status_t ftar_reduce_amax(const void* const* srcs, int k, void* dst, size_t
                              nlevels, true, &r, reinterpret_cast<unsigned*>(amax));
 }
 
+// The scaled cast wide <-> fp8 (cast_kernels.hip): with amax the same two nodes as ftar_reduce_amax, a 4-byte
+// memset of the word and the one kernel.  The pair is checked first, then the pointers; the scale is a device
+// word the kernel reads on the stream, never the host.
+ftar_status_t ftar_cast_scaled(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                               size_t count, const float* scale, float* amax, void* stream) {
+  if (!ftar::cast_pair_supported(src_dtype, dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (count && (!src || !dst)) return FTAR_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(scale) & 3) || (reinterpret_cast<uintptr_t>(amax) & 3)) return FTAR_ERR_INVALID_ARG;
+  if (amax) FTAR_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(float), static_cast<hipStream_t>(stream)));
+  if (count == 0) return FTAR_SUCCESS;
+  return ftar::launch_cast_scaled(src, src_dtype, dst, dst_dtype, count, scale, reinterpret_cast<unsigned*>(amax),
+                                  static_cast<hipStream_t>(stream));
+}
+
 // get_stages (mpi_mod.hpp:1419-1486), minus its two bugs: an unset FT_TOPO
 // is reported (the reference exit(1)s for every P > 1) and a trailing comma
 // does not repeat the last width (the reference's `while(!ss.eof())` does).

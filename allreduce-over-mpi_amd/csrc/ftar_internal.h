@@ -242,6 +242,12 @@ ftar_status_t launch_noop(hipStream_t stream);
 // LDS-staged kernel when source and destination share their 16-byte alignment, else the copy kernel.
 ftar_status_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t stream);  // 0: enough workgroups for one pass
 size_t dtype_size(ftar_dtype_t dt);
+// ftar_cast_scaled's kernels (cast_kernels.hip): dst[i] = cvt_dst(widen(src[i]) * r), r = scale ? *scale : 1.0f
+// read on the device; amax: the word the kernel's workgroups max the stored values' keys into (zeroed by the
+// caller).  The 12 pairs wide (f32, bf16, f16) <-> fp8; any other: FTAR_ERR_UNSUPPORTED before anything else.
+bool cast_pair_supported(ftar_dtype_t src, ftar_dtype_t dst);
+ftar_status_t launch_cast_scaled(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt, size_t count,
+                                 const float* scale, unsigned* amax, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // transports (transport_rccl.cpp, transport_local.cpp, transport_host.cpp; their IPC plumbing: ipc.cpp)

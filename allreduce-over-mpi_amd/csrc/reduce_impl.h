@@ -417,7 +417,9 @@ struct F8SumT {
   __device__ static unsigned s_key(S o) { return o & 0x7fu; }
   __device__ static unsigned key_max(unsigned a, unsigned b) { return pk_umax16(a, b); }
   __device__ static unsigned key_f32(unsigned k) {
-    return __float_as_uint(F::widen((unsigned char)umax(k & 0xffffu, k >> 16)));
+    // the sign masked off: v_cvt_f32_fp8 / _bf8 widen a NaN byte to 0xffc00000, which is no non-negative float's
+    // pattern -- the AllReduce's second round (a signed integer MAX of the ranks' words) dropped it for a 0
+    return __float_as_uint(F::widen((unsigned char)umax(k & 0xffffu, k >> 16))) & 0x7fffffffu;
   }
 };
 // the ring's one-round fold: rounded after every add (H16SumHopT), or, under a scaled finish, before each add

@@ -129,6 +129,7 @@ _lib.ftar_reduce_scaled.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, c
                                     _int, _vp]
 _lib.ftar_reduce_amax.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, ctypes.c_double, ctypes.POINTER(_int),
                                   _int, _vp, _vp]
+_lib.ftar_cast_scaled.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, _vp]
 _lib.ftar_topo_parse.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _int, ctypes.POINTER(Topo)]
 _lib.ftar_topo_from_env.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
 _lib.ftar_topo_choose.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
@@ -349,6 +350,40 @@ def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None, sca
         sh = (_int * max(1, len(shape)))(*shape)
         _check(_lib.ftar_reduce_nested(arr, len(srcs), _ptr(dst), count, _dt(dtype), _op(op), sh, len(shape),
                                        _stream(stream)), "ftar_reduce_nested")
+
+
+# ---- scaled casts wide <-> fp8 ------------------------------------------------
+def cast_scaled(src, dst, count, src_dtype, dst_dtype, scale=None, amax=None, stream=None):
+    """dst[i] = (src[i] as fp32 * scale) rounded to dst_dtype, enqueued on `stream` (ftar_cast_scaled): f32, bf16
+    or f16 to f8e4m3 / f8e5m2, or back.  scale: one fp32 in device memory (pointer or 1-element tensor) the kernel
+    reads on the stream, None = 1.0; amax: a device float that receives the largest |dst[i]| as stored, or None.
+    torch's (src.float() * scale).to(dst_dtype) bit for bit: no saturation (e4m3 overflow is NaN, e5m2 / fp16 inf)."""
+    _check(_lib.ftar_cast_scaled(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _ptr(scale), _ptr(amax),
+                                 _stream(stream)), "ftar_cast_scaled")
+
+
+def _one_f32(t, what, device):
+    import torch
+    if t is None:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != device:
+        raise ValueError(f"{what} must be a 1-element float32 tensor on {device}")
+
+
+def cast_scaled_tensor(src, dst, scale=None, amax=None, stream=None):
+    """cast_scaled on two tensors: the dtypes (torch.float8_e4m3fn / torch.float8_e5m2 included) and the count are
+    the tensors' own.  ValueError unless both are contiguous, of equal numel and on one device, and scale / amax
+    are 1-element fp32 tensors on that device.  Returns dst."""
+    if src.numel() != dst.numel():
+        raise ValueError(f"src has {src.numel()} elements, dst {dst.numel()}")
+    if not src.is_contiguous() or not dst.is_contiguous():
+        raise ValueError("src and dst must be contiguous")
+    if src.device != dst.device:
+        raise ValueError(f"src is on {src.device}, dst on {dst.device}")
+    _one_f32(scale, "scale", src.device)
+    _one_f32(amax, "amax", src.device)
+    cast_scaled(src, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), scale, amax, stream)
+    return dst
 
 
 # ---- topology -------------------------------------------------------------------

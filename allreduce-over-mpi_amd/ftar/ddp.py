@@ -33,6 +33,10 @@ maximum over the buckets in `state.amax`; `state.found_inf()` is the GradScaler-
 Values of the caller's own (a loss scale to agree on) still go through `comm.allreduce_tensor(t, op="max")` /
 `op="min"`.
 
+fp8_compress_hook (with Fp8CompressState, at the end of this module) reduces the same buckets on an fp8 wire:
+quantize with a power-of-two scale (ftar_cast_scaled), AllReduce with op="avg" and amax, dequantize; the scale
+follows the amax one step behind (next_fp8_scale), on the device.
+
 The reference reduces MPI buffers (MPI_Allreduce_FT, mpi_mod.hpp:1723-1778); a DDP bucket is the same call on
 a device tensor, in place (`sendbuf = MPI_IN_PLACE`).
 """
@@ -100,6 +104,130 @@ def allreduce_hook(state, bucket):
     else:
         state.comm.allreduce(None, t, t.numel(), ftar._dt(str(t.dtype)), "avg" if fused else "sum",
                              topo_=state.topo, lonely=state.lonely, stream=stream)
+    state.calls += 1
+    fut = torch.futures.Future(devices=[t.device])
+    fut.set_result(t)
+    return fut
+
+
+# ---- the fp8 wire ---------------------------------------------------------------------------------------
+FP8_MAX = {"e4m3": 448.0, "e5m2": 57344.0}            # the largest finite value of each wire format
+_FP8_DTYPE = {"e4m3": "f8e4m3", "e5m2": "f8e5m2"}
+_BUCKET_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _pow2(k):
+    """2^k as fp32 for an int32 tensor k, clamped to fp32's normal powers of two."""
+    return torch.ldexp(torch.ones_like(k, dtype=torch.float32), k.clamp(-126, 127))
+
+
+def next_fp8_scale(scale, amax, fmt="e4m3", margin=1, backoff=0.5):
+    """The scale of the next step from this step's: a pure function of 1-element fp32 tensors on any device, no
+    host synchronisation.  `scale` is a power of two and `amax` the abs-max of what was stored on the wire, in
+    wire units (scaled values).
+      * amax finite and > 0: the largest power of two p with p * (amax / scale) <= FP8_MAX[fmt] * 2^-margin;
+      * amax inf or NAN (an overflow on the wire): scale * backoff, rounded down to a power of two;
+      * amax 0: scale, unchanged.
+    Clamped to fp32's normal powers of two, 2^-126 .. 2^127.  Exact: mantissas and exponents (torch.frexp), never
+    a rounded quotient or logarithm."""
+    if fmt not in FP8_MAX:
+        raise ValueError(f"fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
+    target = torch.tensor(FP8_MAX[fmt] * 2.0 ** -int(margin), dtype=torch.float32, device=scale.device)
+    finite = torch.isfinite(amax)
+    safe = torch.where(finite & (amax > 0), amax, torch.ones_like(amax))
+    ma, ea = torch.frexp(safe)                     # amax = ma * 2^ea, ma in [0.5, 1)
+    _, es = torch.frexp(scale)                     # scale = 2^(es - 1)
+    mt, et = torch.frexp(target)
+    # p * ma * 2^(ea - es + 1) <= mt * 2^et, and mt / ma lies in (0.5, 2): its largest power of two is 1 or 1/2
+    k = et - (ea - es + 1) - (ma > mt).to(torch.int32)
+    grown = _pow2(k)
+    _, eb = torch.frexp(scale * backoff)           # a value in [2^(eb - 1), 2^eb)
+    backed = _pow2(eb - 1)
+    return torch.where(finite, torch.where(amax > 0, grown, scale), backed)
+
+
+class Fp8CompressState:
+    """What fp8_compress_hook needs: the communicator, the wire format ("e4m3" or "e5m2"), optionally a fixed
+    topology, and the scale policy's two numbers (next_fp8_scale).  On the first bucket's device it keeps
+    `scale` and `inv_scale` (1-element fp32, 1.0 at the start, always powers of two, so scale * inv_scale == 1
+    exactly and quantize -> dequantize loses only the fp8 rounding), `amax` (the running maximum over the buckets
+    since the last reset_amax(), in WIRE units: the scaled mean as stored in fp8) and a grow-only fp8 wire buffer.
+    found_inf() and reset_amax() are HookState's; update_scale(), once per optimizer step, moves the scale on the
+    device.  No host synchronisation anywhere."""
+
+    def __init__(self, comm, fmt="e4m3", topo=None, lonely=0, margin=1, backoff=0.5):
+        if fmt not in FP8_MAX:
+            raise ValueError(f"fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
+        if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
+            raise ValueError(f"margin must be an integer >= 0, not {margin!r}")
+        if isinstance(backoff, bool) or not isinstance(backoff, (int, float)) or not 0 < backoff < 1:
+            raise ValueError(f"backoff must lie in (0, 1), not {backoff!r}")
+        self.comm, self.fmt, self.topo, self.lonely = comm, fmt, topo, lonely
+        self.margin, self.backoff = margin, float(backoff)
+        self.wire_dtype = _FP8_DTYPE[fmt]
+        self.scale = self.inv_scale = self.amax = self._bucket_amax = self._wire = None
+        self.calls = 0
+
+    def _on(self, device, n):
+        if self.scale is None:
+            self.scale = torch.ones(1, dtype=torch.float32, device=device)
+            self.inv_scale = torch.ones(1, dtype=torch.float32, device=device)
+            self.amax = torch.zeros(1, dtype=torch.float32, device=device)
+            self._bucket_amax = torch.zeros(1, dtype=torch.float32, device=device)
+        if self._wire is None or self._wire.numel() < n:
+            self._wire = torch.empty(n, dtype=torch.uint8, device=device)
+        return self._wire
+
+    def _started(self, what):
+        if self.scale is None:
+            raise RuntimeError(f"{what} before the first bucket")
+
+    def reset_amax(self):
+        """Start a new running maximum (once per optimizer step, after found_inf() and update_scale())."""
+        if self.amax is not None:
+            self.amax.zero_()
+
+    def found_inf(self):
+        """A 1-element fp32 device tensor: 1.0 where `amax` is inf or NAN -- a bucket overflowed the wire at the
+        quantize or in a fold, or held a NAN -- else 0.0; no host synchronisation."""
+        self._started("found_inf()")
+        return (~torch.isfinite(self.amax)).to(torch.float32)
+
+    def update_scale(self):
+        """scale = next_fp8_scale(scale, amax, ...), inv_scale = 1 / scale (exact), on the device."""
+        self._started("update_scale()")
+        self.scale.copy_(next_fp8_scale(self.scale, self.amax, self.fmt, self.margin, self.backoff))
+        torch.reciprocal(self.scale, out=self.inv_scale)
+
+
+def fp8_compress_hook(state, bucket):
+    """DDP comm hook: an f32, bf16 or fp16 bucket reduced on an fp8 wire, all on the stream the backward pass runs
+    on: (1) the bucket times state.scale, rounded to the wire format (ftar_cast_scaled); (2) the wire's in-place
+    AllReduce with op="avg" and amax -- the mean is taken inside the last fold, fp32 accumulate and one rounding
+    in the one-round forms; (3) the wire times state.inv_scale back into the bucket; (4) state.amax =
+    maximum(state.amax, this bucket's amax).  Returns a completed future, as allreduce_hook does.
+
+      * state.amax is in WIRE units: the abs-max of the scaled mean as stored in fp8, not of the gradients.
+      * The staged forms round partial sums to fp8 between hops (one rounding per hop or tree node); only the
+        one-round forms sum in fp32 and round once.
+      * Nothing saturates: an overflow at the quantize or in a fold becomes NAN (e4m3) or inf (e5m2) on the wire,
+        reaches state.amax and so found_inf(); the step is then skipped and update_scale() backs the scale off.
+
+    A bucket of any other dtype raises ValueError before any device work."""
+    t = bucket.buffer()
+    if t.dtype not in _BUCKET_DTYPES:
+        raise ValueError(f"fp8_compress_hook takes float32, bfloat16 or float16 buckets, not {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError("fp8_compress_hook needs a contiguous bucket")
+    n = t.numel()
+    stream = torch.cuda.current_stream(t.device)
+    wire = state._on(t.device, n)
+    a = state._bucket_amax
+    dt, f8 = ftar._dt(str(t.dtype)), ftar._dt(state.wire_dtype)
+    ftar.cast_scaled(t, wire, n, dt, f8, scale=state.scale, stream=stream)
+    state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream, amax=a)
+    ftar.cast_scaled(wire, t, n, f8, dt, scale=state.inv_scale, stream=stream)
+    torch.maximum(state.amax, a, out=state.amax)
     state.calls += 1
     fut = torch.futures.Future(devices=[t.device])
     fut.set_result(t)

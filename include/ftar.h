@@ -79,6 +79,7 @@ typedef enum {
  *
  *   amax (ftar_reduce_amax, ftar_allreduce_amax, _amax_group): SUM and AVG of f32 bf16 f16 f8e4m3 f8e5m2;
  *   every other dtype (f64 included: its amax does not fit the word) and every other op is refused.
+ *   cast (ftar_cast_scaled): f32 bf16 f16 -> f8e4m3 f8e5m2 and back, times a device scale; every other pair is refused.
  *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
  * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
@@ -135,6 +136,21 @@ typedef enum {
  * under stream capture FTAR_ERR_UNSUPPORTED with a message (ftar_reduce_amax captures): every refusal comes
  * before any device work and leaves recvbuf and *amax untouched.  The host-buffer entry points
  * (ftar_allreduce_host, _host_group) and the MPI drop-in have no amax variant.
+ *
+ * Scaled casts (ftar_cast_scaled): the two ends of an fp8 wire.  src in {f32, bf16, f16} to dst in {f8e4m3,
+ * f8e5m2} (quantize) and the reverse (dequantize), 12 pairs; every other pair (the same dtype twice, f32 <-> f16,
+ * f64, integers, bool, the unassigned id 11) returns FTAR_ERR_UNSUPPORTED, and that check comes first.  Per
+ * element dst[i] = cvt_dst(widen(src[i]) x r): the widening to fp32 is exact; r is the float at `scale`, read by
+ * the kernel from device memory on the stream (NULL: 1.0f, an exact multiply) and never by the host, so it may be
+ * any bit pattern (0, negative, inf, NaN, subnormal) and the result is what IEEE multiplication gives; the product
+ * is one correctly rounded fp32 multiply, subnormal products kept; cvt_dst is the rounding of the paragraphs above
+ * for that format (f32: the product itself).  That is (src.to(float32) * r).to(dst_dtype) of torch bit for bit:
+ * TWO roundings when dst is narrower than fp32, never one fused one, and no saturation -- e4m3 overflow gives
+ * NaN, e5m2 and f16 overflow +-inf.  amax (optional) is the amax paragraph's word for dst: the IEEE 754-2019
+ * maximum of |dst[i]| as stored, widened exactly to fp32 -- NaN wins, inf is +inf, subnormals kept, all zeros or
+ * count == 0 give bits 0, the word is overwritten.  NULL src or dst with count > 0, or a scale or amax that is not
+ * 4-byte aligned, returns FTAR_ERR_INVALID_ARG; every refusal comes before any device work and leaves dst and
+ * *amax untouched.  src and dst must not overlap.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
@@ -204,6 +220,15 @@ ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size
  * kernel, so it captures into a HIP graph as those two nodes. */
 ftar_status_t ftar_reduce_amax(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                double scale, const int* shape, int nlevels, float* amax, void* stream);
+/* Scaled cast between a wide float and an fp8 format (extension; the scaled-casts paragraph above):
+ * dst[i] = round_to_dst(fp32(src[i]) x *scale) for i < count, one streaming kernel on `stream`.  scale: one float
+ * in device memory on the current device, 4-byte aligned, read by the kernel (NULL: 1.0).  amax: as in
+ * ftar_reduce_amax, or NULL; with it the call enqueues a 4-byte memset of *amax and the kernel, and captures into
+ * a HIP graph as those two nodes (without it: the kernel alone, storing the same bits).  count == 0 succeeds and a
+ * non-NULL amax then holds +0.0.  Pointers need no alignment beyond their element's: pairs whose 16-byte
+ * alignments do not fit each other run an element-wise kernel. */
+ftar_status_t ftar_cast_scaled(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                               size_t count, const float* scale, float* amax, void* stream);
 
 /* ---- topology ------------------------------------------------------------
  * ftar_topo_parse: FT_TOPO / FT_LONELY strings (NULL = unset) for nranks.
