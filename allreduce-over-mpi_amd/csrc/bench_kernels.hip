@@ -567,3 +567,138 @@ extern "C" ftar_status_t ftar_debug_cast_variant(int layout, int u, const void* 
   FTAR_CHECK_HIP(e);
   return FTAR_SUCCESS;
 }
+
+// ---------------------------------------------------------------------------
+// Stochastic rounding (ftar_cast_scaled_sr): the hooks of tools/sr_sweep.py and tests/test_gpu_cast_sr.py.
+// ---------------------------------------------------------------------------
+// The production stochastic cast (same kernels, layout and narrowing device function) on an explicit array of
+// words, words[i] for element i, in place of the generator.  Quantize pairs only; no amax.
+extern "C" ftar_status_t ftar_bench_cast_sr_words(const void* src, int src_dtype, void* dst, int dst_dtype,
+                                                  size_t count, const float* scale, const unsigned* words,
+                                                  void* stream) {
+  using namespace ftar;
+  if (!is_cast_wide((ftar_dtype_t)src_dtype) || !is_f8((ftar_dtype_t)dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!src || !dst || !words || !count) return FTAR_ERR_INVALID_ARG;
+  FTAR_CHECK_HIP((launch_cast_any<kCastU16, kCastU32, kCastLayout, SrWords>(
+      src, (ftar_dtype_t)src_dtype, dst, (ftar_dtype_t)dst_dtype, count, scale, nullptr,
+      static_cast<hipStream_t>(stream), SrWords::Arg{words, count})));
+  return FTAR_SUCCESS;
+}
+
+namespace ftar {
+namespace {
+// The contract of ftar.h's stochastic-rounding paragraph in integers, step by step as written there (e, ulp, lo,
+// F, the carry): what SrFmt (the instruction, and float arithmetic below the smallest normal) is held against.
+// *f_out: F.
+template <bool E5M2>
+__device__ unsigned sr_contract(unsigned bits, unsigned u, unsigned* f_out) {
+  constexpr int M = E5M2 ? 2 : 3, BIAS = E5M2 ? 15 : 7, EMIN = 1 - BIAS;
+  const unsigned a = bits & 0x7fffffffu, sign = (bits >> 24) & 0x80u;
+  *f_out = 0;
+  if (a > 0x7f800000u) return sign | 0x7fu;
+  if (a == 0x7f800000u) return sign | (E5M2 ? 0x7cu : 0x7fu);
+  if (a == 0) return sign;
+  const int ee = (a >> 23) ? (int)(a >> 23) : 1;
+  const unsigned long long sig = (a & 0x7fffffu) | ((a >> 23) ? 0x800000u : 0u);   // a = sig * 2^(ee - 150)
+  const int e = ee - 127, q = (e > EMIN ? e : EMIN) - M;                            // ulp = 2^q
+  const int k = q - (ee - 150);                                                     // a / ulp = sig / 2^k, k >= 20
+  const unsigned long long lo = k < 64 ? sig >> k : 0, rem = k < 64 ? sig & ((1ull << k) - 1) : sig;
+  unsigned long long F;
+  if (k <= 32) F = rem << (32 - k);
+  else F = (k - 32) < 64 ? rem >> (k - 32) : 0;
+  *f_out = (unsigned)F;
+  const unsigned long long units = lo + (((unsigned long long)u + F) >> 32);
+  unsigned enc;
+  if (e < EMIN) enc = (unsigned)units;                                               // subnormal range
+  else enc = ((unsigned)(e + BIAS) << M) + (unsigned)(units - (1u << M));
+  constexpr unsigned TOP = E5M2 ? 0x7cu : 0x7fu;
+  return sign | (enc < TOP ? enc : TOP);
+}
+constexpr int kSweepModes = 3, kSweepWords = 6;
+// modes: 0 the production narrowing (SrFmt::pack in every byte position and SrFmt::narrow), 1 the bare
+// instruction fed U, 2 the bare instruction fed U >> (32 - d), d = 23 - m.  words: 0, 1, 2^31, 2^32 - 1, the
+// input's threshold 2^32 - F and 2^32 - F - 1.  bad[mode][word][fp32 exponent field], ex[mode][exponent][4] =
+// {input bits, word, got, want} of one mismatch (ex[..][0] == 0xffffffff: none yet).
+template <bool E5M2>
+__global__ void __launch_bounds__(256) sr_sweep_kernel(unsigned long long first, unsigned long long count,
+                                                       unsigned long long* bad, unsigned* ex) {
+  using F = SrFmt<E5M2>;
+  constexpr int SH = 32 - F::kDrop;
+  __shared__ unsigned bins[kSweepModes * kSweepWords * 256];
+  for (int j = threadIdx.x; j < kSweepModes * kSweepWords * 256; j += 256) bins[j] = 0;
+  __syncthreads();
+  const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+    const unsigned b = (unsigned)(first + i), ebin = (b >> 23) & 0xffu;
+    const float p = __uint_as_float(b);
+    unsigned f;
+    sr_contract<E5M2>(b, 0u, &f);
+    const unsigned w[kSweepWords] = {0u, 1u, 0x80000000u, 0xffffffffu, 0u - f, 0u - f - 1u};
+    const unsigned pk0 = F::pack(f32x4{p, p, p, p}, u32x4{w[0], w[1], w[2], w[3]});
+    const unsigned pk1 = F::pack(f32x4{p, p, p, p}, u32x4{w[4], w[5], w[0], w[1]});
+#pragma unroll
+    for (int j = 0; j < kSweepWords; ++j) {
+      unsigned dummy;
+      const unsigned want = sr_contract<E5M2>(b, w[j], &dummy);
+      unsigned got[kSweepModes];
+      got[0] = j < 4 ? (pk0 >> (8 * j)) & 0xffu : (pk1 >> (8 * (j - 4))) & 0xffu;
+      if (f8_bits_differ<E5M2>(F::narrow(p, w[j]), want)) got[0] = 0x100u | F::narrow(p, w[j]);
+      if (j < 2 && f8_bits_differ<E5M2>((pk1 >> (8 * (j + 2))) & 0xffu, want)) got[0] = 0x200u | ((pk1 >> (8 * (j + 2))) & 0xffu);
+      if constexpr (E5M2) {
+        got[1] = __builtin_amdgcn_cvt_sr_bf8_f32(p, w[j], 0u, 0) & 0xffu;
+        got[2] = __builtin_amdgcn_cvt_sr_bf8_f32(p, w[j] >> SH, 0u, 0) & 0xffu;
+      } else {
+        got[1] = __builtin_amdgcn_cvt_sr_fp8_f32(p, w[j], 0u, 0) & 0xffu;
+        got[2] = __builtin_amdgcn_cvt_sr_fp8_f32(p, w[j] >> SH, 0u, 0) & 0xffu;
+      }
+#pragma unroll
+      for (int m = 0; m < kSweepModes; ++m) {
+        if (got[m] > 0xffu || f8_bits_differ<E5M2>(got[m], want)) {
+          atomicAdd(&bins[(m * kSweepWords + j) * 256 + ebin], 1u);
+          unsigned* slot = ex + (m * 256 + ebin) * 4;
+          if (atomicCAS(slot, 0xffffffffu, b) == 0xffffffffu) {
+            slot[1] = w[j];
+            slot[2] = got[m];
+            slot[3] = want;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < kSweepModes * kSweepWords * 256; j += 256)
+    if (bins[j]) atomicAdd(bad + j, (unsigned long long)bins[j]);
+}
+}  // namespace
+}  // namespace ftar
+
+// tools/sr_sweep.py's hook: the fp32 bit patterns [first, first + count) through the stochastic narrowing to e4m3
+// (e5m2 != 0: e5m2) in the three modes and six words of sr_sweep_kernel, against the contract in integers.
+// mismatches: 3 x 6 x 256 counts, added to; examples: 3 x 256 x 4 words, 0xffffffff where none was seen (both host
+// arrays the caller initialises).  NaNs compare as NaN or not.  An input whose stored pattern 0xffffffff would be
+// taken for "none" is a NaN, whose exponent bin 255 then only shows in the counts.
+extern "C" ftar_status_t ftar_bench_sr_sweep(int e5m2, unsigned long long first, unsigned long long count,
+                                             unsigned long long* mismatches, unsigned* examples) {
+  using namespace ftar;
+  if (!mismatches || !examples || first + count > (1ull << 32)) return FTAR_ERR_INVALID_ARG;
+  constexpr size_t NB = (size_t)kSweepModes * kSweepWords * 256 * sizeof(unsigned long long);
+  constexpr size_t NE = (size_t)kSweepModes * 256 * 4 * sizeof(unsigned);
+  unsigned long long* d_bad = nullptr;
+  unsigned* d_ex = nullptr;
+  ftar_status_t st = FTAR_SUCCESS;
+  if (hipMalloc(&d_bad, NB) != hipSuccess || hipMalloc(&d_ex, NE) != hipSuccess) st = FTAR_ERR_NO_MEMORY;
+  if (st == FTAR_SUCCESS && (hipMemcpy(d_bad, mismatches, NB, hipMemcpyHostToDevice) != hipSuccess ||
+                             hipMemcpy(d_ex, examples, NE, hipMemcpyHostToDevice) != hipSuccess))
+    st = FTAR_ERR_HIP;
+  if (st == FTAR_SUCCESS && count) {
+    if (e5m2) hipLaunchKernelGGL(sr_sweep_kernel<true>, dim3(4096), dim3(256), 0, nullptr, first, count, d_bad, d_ex);
+    else hipLaunchKernelGGL(sr_sweep_kernel<false>, dim3(4096), dim3(256), 0, nullptr, first, count, d_bad, d_ex);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = FTAR_ERR_HIP;
+  }
+  if (st == FTAR_SUCCESS && (hipMemcpy(mismatches, d_bad, NB, hipMemcpyDeviceToHost) != hipSuccess ||
+                             hipMemcpy(examples, d_ex, NE, hipMemcpyDeviceToHost) != hipSuccess))
+    st = FTAR_ERR_HIP;
+  hip_ignore(hipFree(d_bad));
+  hip_ignore(hipFree(d_ex));
+  return st;
+}

@@ -253,6 +253,22 @@ ftar_status_t ftar_cast_scaled(const void* src, ftar_dtype_t src_dtype, void* ds
                                   static_cast<hipStream_t>(stream));
 }
 
+// The same with the stochastic narrowing (quantize pairs only): the seed is a device word like the scale, the
+// offset the global index of element 0.  Refusals in the header's order, all before the memset.
+ftar_status_t ftar_cast_scaled_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                                  size_t count, const float* scale, const uint64_t* seed, uint64_t offset,
+                                  float* amax, void* stream) {
+  if (!ftar::cast_sr_pair_supported(src_dtype, dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!seed || (reinterpret_cast<uintptr_t>(seed) & 7)) return FTAR_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(scale) & 3) || (reinterpret_cast<uintptr_t>(amax) & 3)) return FTAR_ERR_INVALID_ARG;
+  if (count && (!src || !dst)) return FTAR_ERR_INVALID_ARG;
+  if (amax) FTAR_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(float), static_cast<hipStream_t>(stream)));
+  if (count == 0) return FTAR_SUCCESS;
+  return ftar::launch_cast_scaled_sr(src, src_dtype, dst, dst_dtype, count, scale,
+                                     reinterpret_cast<const unsigned long long*>(seed), offset,
+                                     reinterpret_cast<unsigned*>(amax), static_cast<hipStream_t>(stream));
+}
+
 // get_stages (mpi_mod.hpp:1419-1486), minus its two bugs: an unset FT_TOPO
 // is reported (the reference exit(1)s for every P > 1) and a trailing comma
 // does not repeat the last width (the reference's `while(!ss.eof())` does).

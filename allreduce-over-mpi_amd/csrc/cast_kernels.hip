@@ -4,15 +4,6 @@
 
 namespace ftar {
 
-namespace {
-// The layout and the fp8 vectors per lane and pass, measured cold on 256 MiB of wide data (tools/cast_rates.py;
-// DESIGN §4 has every candidate's rate, profiles/cast/ the logs): lane-contiguous 16-byte wide accesses with 4- /
-// 8-byte fp8 accesses won or tied every pair against the lane-owned vectors, staged through LDS or not (whose
-// lane-strided wide stores ran f8 -> f32 at 1.5 TB/s); f8 -> f32 gained 8 % from 4 vectors per lane over 2.
-constexpr int kCastLayout = kLayWide;
-constexpr int kCastU16 = 2, kCastU32 = 4;
-}  // namespace
-
 bool cast_pair_supported(ftar_dtype_t src, ftar_dtype_t dst) {
   return (is_cast_wide(src) && is_f8(dst)) || (is_f8(src) && is_cast_wide(dst));
 }
@@ -23,6 +14,19 @@ ftar_status_t launch_cast_scaled(const void* src, ftar_dtype_t src_dt, void* dst
   if (count == 0) return FTAR_SUCCESS;
   if (!src || !dst) return FTAR_ERR_INVALID_ARG;
   FTAR_CHECK_HIP((launch_cast_any<kCastU16, kCastU32, kCastLayout>(src, src_dt, dst, dst_dt, count, scale, amax, s)));
+  return FTAR_SUCCESS;
+}
+
+bool cast_sr_pair_supported(ftar_dtype_t src, ftar_dtype_t dst) { return is_cast_wide(src) && is_f8(dst); }
+
+ftar_status_t launch_cast_scaled_sr(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt,
+                                    size_t count, const float* scale, const unsigned long long* seed,
+                                    unsigned long long offset, unsigned* amax, hipStream_t s) {
+  if (!cast_sr_pair_supported(src_dt, dst_dt)) return FTAR_ERR_UNSUPPORTED;
+  if (count == 0) return FTAR_SUCCESS;
+  if (!src || !dst || !seed) return FTAR_ERR_INVALID_ARG;
+  FTAR_CHECK_HIP((launch_cast_any<kCastU16, kCastU32, kCastLayout, SrGen>(src, src_dt, dst, dst_dt, count, scale, amax,
+                                                                          s, SrGen::Arg{seed, offset})));
   return FTAR_SUCCESS;
 }
 

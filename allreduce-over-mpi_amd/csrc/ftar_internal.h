@@ -248,6 +248,12 @@ size_t dtype_size(ftar_dtype_t dt);
 bool cast_pair_supported(ftar_dtype_t src, ftar_dtype_t dst);
 ftar_status_t launch_cast_scaled(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt, size_t count,
                                  const float* scale, unsigned* amax, hipStream_t stream);
+// ftar_cast_scaled_sr's: the six quantize pairs with the stochastic narrowing sr_dst(p, U(*seed, offset + i)), the
+// seed read on the device; a dequantize pair or any other: FTAR_ERR_UNSUPPORTED before anything else.
+bool cast_sr_pair_supported(ftar_dtype_t src, ftar_dtype_t dst);
+ftar_status_t launch_cast_scaled_sr(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt,
+                                    size_t count, const float* scale, const unsigned long long* seed,
+                                    unsigned long long offset, unsigned* amax, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // transports (transport_rccl.cpp, transport_local.cpp, transport_host.cpp; their IPC plumbing: ipc.cpp)

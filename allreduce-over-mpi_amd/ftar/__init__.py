@@ -130,6 +130,7 @@ _lib.ftar_reduce_scaled.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, c
 _lib.ftar_reduce_amax.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, ctypes.c_double, ctypes.POINTER(_int),
                                   _int, _vp, _vp]
 _lib.ftar_cast_scaled.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, _vp]
+_lib.ftar_cast_scaled_sr.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, ctypes.c_uint64, _vp, _vp]
 _lib.ftar_topo_parse.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _int, ctypes.POINTER(Topo)]
 _lib.ftar_topo_from_env.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
 _lib.ftar_topo_choose.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
@@ -223,7 +224,8 @@ _bench_lib = None
 
 def bench_lib():
     """libftar_bench.so: the A/B kernel variants (ftar_debug_reduce_variant, ftar_debug_reduce_nested_lds) and
-    kernel test hooks (ftar_debug_bf16_cvt_check, ftar_debug_f16_cvt_check, ftar_debug_f8_cvt_check) that tools/kbench*.py and the tests load; kept out of the
+    kernel test hooks (ftar_debug_bf16_cvt_check, ftar_debug_f16_cvt_check, ftar_debug_f8_cvt_check,
+    ftar_bench_cast_sr_words, ftar_bench_sr_sweep) that tools/kbench*.py and the tests load; kept out of the
     product library, which holds only the kernels the engine dispatches."""
     global _bench_lib
     if _bench_lib is None:
@@ -353,27 +355,58 @@ def reduce(srcs, dst, count, dtype="f32", op="sum", stream=None, shape=None, sca
 
 
 # ---- scaled casts wide <-> fp8 ------------------------------------------------
-def cast_scaled(src, dst, count, src_dtype, dst_dtype, scale=None, amax=None, stream=None):
+ROUNDINGS = ("nearest", "stochastic")
+
+
+def _rounding(rounding, seed):
+    """True for "stochastic" (which needs a seed), False for "nearest"; anything else is a ValueError."""
+    if rounding not in ROUNDINGS:
+        raise ValueError(f"rounding must be 'nearest' or 'stochastic', not {rounding!r}")
+    if rounding == "stochastic" and seed is None:
+        raise ValueError("rounding='stochastic' needs a seed in device memory")
+    return rounding == "stochastic"
+
+
+def cast_scaled(src, dst, count, src_dtype, dst_dtype, scale=None, amax=None, stream=None, rounding="nearest",
+                seed=None, offset=0):
     """dst[i] = (src[i] as fp32 * scale) rounded to dst_dtype, enqueued on `stream` (ftar_cast_scaled): f32, bf16
     or f16 to f8e4m3 / f8e5m2, or back.  scale: one fp32 in device memory (pointer or 1-element tensor) the kernel
     reads on the stream, None = 1.0; amax: a device float that receives the largest |dst[i]| as stored, or None.
-    torch's (src.float() * scale).to(dst_dtype) bit for bit: no saturation (e4m3 overflow is NaN, e5m2 / fp16 inf)."""
+    torch's (src.float() * scale).to(dst_dtype) bit for bit: no saturation (e4m3 overflow is NaN, e5m2 / fp16 inf).
+    rounding="stochastic" (quantize pairs only; ftar_cast_scaled_sr): each element goes to one of its two fp8
+    neighbours with the expectation of the product, decided by a 32-bit word that is a pure function of the
+    64-bit value at `seed` (device memory, 8-byte aligned: a pointer or a 1-element int64 tensor) and of the global
+    element index offset + i.  Any other `rounding`, or "stochastic" without a seed, raises ValueError before any
+    device work."""
+    if _rounding(rounding, seed):
+        _check(_lib.ftar_cast_scaled_sr(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _ptr(scale),
+                                        _ptr(seed), int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(amax), _stream(stream)),
+               "ftar_cast_scaled_sr")
+        return
     _check(_lib.ftar_cast_scaled(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _ptr(scale), _ptr(amax),
                                  _stream(stream)), "ftar_cast_scaled")
 
 
-def _one_f32(t, what, device):
+def _one_elem(t, what, device, dtype):
     import torch
     if t is None:
         return
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or t.device != device:
-        raise ValueError(f"{what} must be a 1-element float32 tensor on {device}")
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.numel() != 1 or t.device != device:
+        raise ValueError(f"{what} must be a 1-element {str(dtype).replace('torch.', '')} tensor on {device}")
 
 
-def cast_scaled_tensor(src, dst, scale=None, amax=None, stream=None):
+def _one_f32(t, what, device):
+    import torch
+    _one_elem(t, what, device, torch.float32)
+
+
+def cast_scaled_tensor(src, dst, scale=None, amax=None, stream=None, rounding="nearest", seed=None, offset=0):
     """cast_scaled on two tensors: the dtypes (torch.float8_e4m3fn / torch.float8_e5m2 included) and the count are
-    the tensors' own.  ValueError unless both are contiguous, of equal numel and on one device, and scale / amax
-    are 1-element fp32 tensors on that device.  Returns dst."""
+    the tensors' own.  ValueError unless both are contiguous, of equal numel and on one device, scale / amax
+    are 1-element fp32 tensors on that device and, with rounding="stochastic", seed is a 1-element int64 tensor
+    there.  Returns dst."""
+    import torch
+    stochastic = _rounding(rounding, seed)
     if src.numel() != dst.numel():
         raise ValueError(f"src has {src.numel()} elements, dst {dst.numel()}")
     if not src.is_contiguous() or not dst.is_contiguous():
@@ -382,7 +415,10 @@ def cast_scaled_tensor(src, dst, scale=None, amax=None, stream=None):
         raise ValueError(f"src is on {src.device}, dst on {dst.device}")
     _one_f32(scale, "scale", src.device)
     _one_f32(amax, "amax", src.device)
-    cast_scaled(src, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), scale, amax, stream)
+    if stochastic:
+        _one_elem(seed, "seed", src.device, torch.int64)
+    cast_scaled(src, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), scale, amax, stream, rounding,
+                seed if stochastic else None, offset)
     return dst
 
 

@@ -34,8 +34,8 @@ Values of the caller's own (a loss scale to agree on) still go through `comm.all
 `op="min"`.
 
 fp8_compress_hook (with Fp8CompressState, at the end of this module) reduces the same buckets on an fp8 wire:
-quantize with a power-of-two scale (ftar_cast_scaled), AllReduce with op="avg" and amax, dequantize; the scale
-follows the amax one step behind (next_fp8_scale), on the device.
+quantize with a power-of-two scale (ftar_cast_scaled, or with rounding="stochastic" ftar_cast_scaled_sr), AllReduce
+with op="avg" and amax, dequantize; the scale follows the amax one step behind (next_fp8_scale), on the device.
 
 The reference reduces MPI buffers (MPI_Allreduce_FT, mpi_mod.hpp:1723-1778); a DDP bucket is the same call on
 a device tensor, in place (`sendbuf = MPI_IN_PLACE`).
@@ -146,6 +146,16 @@ def next_fp8_scale(scale, amax, fmt="e4m3", margin=1, backoff=0.5):
     return torch.where(finite, torch.where(amax > 0, grown, scale), backed)
 
 
+def rank_seed(seed, rank):
+    """The 64-bit device seed of one rank: the splitmix64 finaliser of seed + (rank + 1) golden gammas, i.e. the
+    (rank + 1)-th output of splitmix64 started at `seed`; so ranks, and neighbouring seeds, get unrelated streams."""
+    m = (1 << 64) - 1
+    z = (int(seed) + (int(rank) + 1) * 0x9E3779B97F4A7C15) & m
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+    return z ^ (z >> 31)
+
+
 class Fp8CompressState:
     """What fp8_compress_hook needs: the communicator, the wire format ("e4m3" or "e5m2"), optionally a fixed
     topology, and the scale policy's two numbers (next_fp8_scale).  On the first bucket's device it keeps
@@ -153,17 +163,33 @@ class Fp8CompressState:
     exactly and quantize -> dequantize loses only the fp8 rounding), `amax` (the running maximum over the buckets
     since the last reset_amax(), in WIRE units: the scaled mean as stored in fp8) and a grow-only fp8 wire buffer.
     found_inf() and reset_amax() are HookState's; update_scale(), once per optimizer step, moves the scale on the
-    device.  No host synchronisation anywhere."""
+    device.  No host synchronisation anywhere.
 
-    def __init__(self, comm, fmt="e4m3", topo=None, lonely=0, margin=1, backoff=0.5):
+    rounding="stochastic": the quantize rounds each element to one of its two fp8 neighbours with the expectation
+    of the scaled value (ftar_cast_scaled_sr), so its error is zero-mean and averages down over ranks and steps
+    where round-to-nearest pushes every rank the same way.  The state then keeps `seed`, a 1-element int64 device
+    tensor derived once on the host from (seed, comm.rank) through the splitmix64 finaliser (rank_seed): ranks get
+    unrelated streams.  It also keeps `offset`, a host-side count of the elements quantized so far, which grows by
+    the bucket's numel per bucket and is never reset, so no two buckets of a run share a word.  Under graph
+    capture the offset is baked into the captured kernel: a caller who replays a captured hook must change
+    state.seed on the device between replays (e.g. state.seed.add_(1)), or every replay rounds the same way."""
+
+    def __init__(self, comm, fmt="e4m3", topo=None, lonely=0, margin=1, backoff=0.5, rounding="nearest", seed=0):
         if fmt not in FP8_MAX:
             raise ValueError(f"fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
         if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
             raise ValueError(f"margin must be an integer >= 0, not {margin!r}")
         if isinstance(backoff, bool) or not isinstance(backoff, (int, float)) or not 0 < backoff < 1:
             raise ValueError(f"backoff must lie in (0, 1), not {backoff!r}")
+        if rounding not in ftar.ROUNDINGS:
+            raise ValueError(f"rounding must be 'nearest' or 'stochastic', not {rounding!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an integer, not {seed!r}")
         self.comm, self.fmt, self.topo, self.lonely = comm, fmt, topo, lonely
         self.margin, self.backoff = margin, float(backoff)
+        self.rounding, self.base_seed = rounding, seed
+        self.seed = None      # stochastic: the rank's device seed, created with the scale
+        self.offset = 0
         self.wire_dtype = _FP8_DTYPE[fmt]
         self.scale = self.inv_scale = self.amax = self._bucket_amax = self._wire = None
         self.calls = 0
@@ -174,6 +200,9 @@ class Fp8CompressState:
             self.inv_scale = torch.ones(1, dtype=torch.float32, device=device)
             self.amax = torch.zeros(1, dtype=torch.float32, device=device)
             self._bucket_amax = torch.zeros(1, dtype=torch.float32, device=device)
+            if self.rounding == "stochastic":
+                word = rank_seed(self.base_seed, getattr(self.comm, "rank", 0))
+                self.seed = torch.tensor([word - (1 << 64) if word >> 63 else word], dtype=torch.int64, device=device)
         if self._wire is None or self._wire.numel() < n:
             self._wire = torch.empty(n, dtype=torch.uint8, device=device)
         return self._wire
@@ -202,7 +231,8 @@ class Fp8CompressState:
 
 def fp8_compress_hook(state, bucket):
     """DDP comm hook: an f32, bf16 or fp16 bucket reduced on an fp8 wire, all on the stream the backward pass runs
-    on: (1) the bucket times state.scale, rounded to the wire format (ftar_cast_scaled); (2) the wire's in-place
+    on: (1) the bucket times state.scale, rounded to the wire format (ftar_cast_scaled; with
+    state.rounding == "stochastic" ftar_cast_scaled_sr on state.seed at the running state.offset); (2) the wire's in-place
     AllReduce with op="avg" and amax -- the mean is taken inside the last fold, fp32 accumulate and one rounding
     in the one-round forms; (3) the wire times state.inv_scale back into the bucket; (4) state.amax =
     maximum(state.amax, this bucket's amax).  Returns a completed future, as allreduce_hook does.
@@ -224,7 +254,12 @@ def fp8_compress_hook(state, bucket):
     wire = state._on(t.device, n)
     a = state._bucket_amax
     dt, f8 = ftar._dt(str(t.dtype)), ftar._dt(state.wire_dtype)
-    ftar.cast_scaled(t, wire, n, dt, f8, scale=state.scale, stream=stream)
+    if state.rounding == "stochastic":
+        ftar.cast_scaled(t, wire, n, dt, f8, scale=state.scale, stream=stream, rounding="stochastic", seed=state.seed,
+                         offset=state.offset)
+        state.offset += n
+    else:
+        ftar.cast_scaled(t, wire, n, dt, f8, scale=state.scale, stream=stream)
     state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream, amax=a)
     ftar.cast_scaled(wire, t, n, f8, dt, scale=state.inv_scale, stream=stream)
     torch.maximum(state.amax, a, out=state.amax)

@@ -80,6 +80,7 @@ typedef enum {
  *   amax (ftar_reduce_amax, ftar_allreduce_amax, _amax_group): SUM and AVG of f32 bf16 f16 f8e4m3 f8e5m2;
  *   every other dtype (f64 included: its amax does not fit the word) and every other op is refused.
  *   cast (ftar_cast_scaled): f32 bf16 f16 -> f8e4m3 f8e5m2 and back, times a device scale; every other pair is refused.
+ *   stochastic cast (ftar_cast_scaled_sr): f32 bf16 f16 -> f8e4m3 f8e5m2 only; the way back and every other pair is refused.
  *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
  * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
@@ -151,6 +152,40 @@ typedef enum {
  * count == 0 give bits 0, the word is overwritten.  NULL src or dst with count > 0, or a scale or amax that is not
  * 4-byte aligned, returns FTAR_ERR_INVALID_ARG; every refusal comes before any device work and leaves dst and
  * *amax untouched.  src and dst must not overlap.
+ *
+ * Stochastic rounding (ftar_cast_scaled_sr): the six quantize pairs of the scaled cast with another narrowing,
+ * dst[i] = sr_dst(mul_rn_f32(widen(src[i]), r), U(seed, offset + i)).  Widening, r and the multiply are exactly
+ * ftar_cast_scaled's (exact; NULL scale is 1.0f; one correctly rounded fp32 multiply in a register of its own).
+ * sr_dst(p, U), U a 32-bit word: a NaN p gives NaN (which pattern is unspecified); +-0 gives +-0, and the sign is
+ * kept also when a non-zero p rounds down to zero; +-inf gives e5m2 +-inf and e4m3 NaN.  Otherwise, with a = |p|,
+ * m = 3 (e4m3) or 2 (e5m2), emin = -6 or -14, e = floor(log2 a), ulp = 2^(max(e, emin) - m),
+ * lo = floor(a / ulp) x ulp, frac = (a - lo) / ulp in [0, 1) and F = floor(frac x 2^32), the magnitude stored is
+ * lo + ulp if U + F >= 2^32, else lo.  In integers: the dropped mantissa bits are aligned under the TOP of U and
+ * the carry decides -- with d = 23 - m dropped bits in the normal range, ((bits & (2^d - 1)) << (32 - d)) + U >= 2^32;
+ * in the subnormal range d grows and bits below 2^-32 ulp are dropped.  So a representable p is stored unchanged
+ * for every U, U = 0 truncates toward zero, and the stored value's expectation over a uniform U is p (to 2^-32 ulp).
+ * No saturation: the carry runs into the next encoding -- an e4m3 magnitude in (448, 480) becomes NaN with
+ * probability frac and from 480 on always; an e5m2 magnitude in (57344, 65536) becomes +-inf with probability
+ * frac and from 65536 on always -- so an overflow stays visible to amax.
+ * The word is a pure function of two inputs: the 64-bit value s at `seed` (device memory, 8-byte aligned, read by
+ * the kernel on the stream, never by the host) and the global element index g = offset + i (mod 2^64).  It does
+ * not depend on pointer alignment, on the kernel or layout that ran, on the grid, or on how a range was split
+ * into calls: casting [0, n) in one call stores the bits of casting [0, a) and [a, n) with offset = a.  Exactly,
+ * in unsigned arithmetic of the stated widths:
+ *   z = s + 0x9E3779B97F4A7C15            (64-bit; then the splitmix64 finaliser)
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31)
+ *   ka = low 32 bits of z, kb = high 32 bits of z;  gl = low 32 bits of g, gh = high 32 bits of g
+ *   x = gl ^ ka                           (32-bit from here)
+ *   x = (x ^ (x >> 16)) * 0x7feb352d
+ *   x = x + (kb ^ (gh * 0x9E3779B9))
+ *   x = (x ^ (x >> 15)) * 0x846ca68b
+ *   U = x ^ (x >> 16)
+ * Both keys change with every bit of s, and kb enters between the two rounds, so the streams of two seeds (s and
+ * s + 1 included) are neither shifts nor index permutations of each other.  amax is ftar_cast_scaled's.  A
+ * dequantize pair, or any pair ftar_cast_scaled refuses, returns FTAR_ERR_UNSUPPORTED, and that check comes first;
+ * a NULL seed, a seed not 8-byte aligned, a scale or amax not 4-byte aligned, or a NULL src or dst with
+ * count > 0 returns FTAR_ERR_INVALID_ARG; every refusal comes before any device work and leaves dst and *amax
+ * untouched.  count == 0 succeeds, and a non-NULL amax then holds +0.0.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
@@ -229,6 +264,15 @@ ftar_status_t ftar_reduce_amax(const void* const* srcs, int k, void* dst, size_t
  * alignments do not fit each other run an element-wise kernel. */
 ftar_status_t ftar_cast_scaled(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
                                size_t count, const float* scale, float* amax, void* stream);
+/* ftar_cast_scaled's quantize with stochastic rounding (extension; the stochastic-rounding paragraph above):
+ * dst[i] = sr_dst(fp32(src[i]) x *scale, U(*seed, offset + i)), src in {f32, bf16, f16}, dst in {f8e4m3, f8e5m2}.
+ * seed: one uint64_t in device memory on the current device, 8-byte aligned, read by the kernel; offset: the
+ * global index of element 0, so consecutive calls with a running offset never reuse a word.  scale, amax, count
+ * == 0, pointer alignment and graph capture (a 4-byte memset and one kernel with amax, the kernel alone without)
+ * as for ftar_cast_scaled. */
+ftar_status_t ftar_cast_scaled_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                                  size_t count, const float* scale, const uint64_t* seed, uint64_t offset,
+                                  float* amax, void* stream);
 
 /* ---- topology ------------------------------------------------------------
  * ftar_topo_parse: FT_TOPO / FT_LONELY strings (NULL = unset) for nranks.

@@ -6,6 +6,9 @@ written, median of interleaved rounds with the slowest and fastest round next to
 
   f32>f8e4m3          the production dispatch (ftar.cast_scaled), every one of the 12 pairs by default
   f32>f8e4m3+amax     the same with the amax word (a 4-byte memset and the amax kernel)
+  f32>f8e4m3+sr       the stochastic-rounding quantize (ftar_cast_scaled_sr, rounding="stochastic") of the six
+                      quantize pairs (--sr), interleaved with the RNE quantize of the same pair, its yardstick;
+                      the last lines give each pair's ratio of medians
   f32>f8e4m3@L.U      layout candidate L (0 lane-owned vectors, 1 the same staged through LDS, 2 lane-contiguous
                       wide vectors with 4- / 8-byte fp8 accesses) at U vectors per lane and pass, through
                       libftar_bench.so's ftar_debug_cast_variant (--layouts)
@@ -15,7 +18,7 @@ written, median of interleaved rounds with the slowest and fastest round next to
                       kernel, the margin for "as fast as the copy"
 
 Random bytes on both sides, so lanes hold NaN and inf too: the instructions do not care.
-python tools/cast_rates.py [--pairs f32>f8e4m3,...] [--layouts] [--amax] [--rounds 5] [--reps 8]"""
+python tools/cast_rates.py [--pairs f32>f8e4m3,...] [--layouts] [--amax] [--sr] [--rounds 5] [--reps 8]"""
 import argparse
 import ctypes
 import json
@@ -36,6 +39,7 @@ ap.add_argument("--pairs", default=",".join(ALL))
 ap.add_argument("--layouts", action="store_true", help="also every layout candidate of --layout-pairs")
 ap.add_argument("--layout-pairs", default="f32>f8e4m3,bf16>f8e4m3,f8e4m3>f32,f8e4m3>bf16")
 ap.add_argument("--amax", action="store_true", help="also every pair with the amax word")
+ap.add_argument("--sr", action="store_true", help="also every quantize pair with stochastic rounding")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=8)
 a = ap.parse_args()
@@ -45,6 +49,7 @@ bufs = [[torch.randint(0, 256, (NB,), dtype=torch.uint8, device="cuda") for _ in
 stream = torch.cuda.current_stream()
 scale = torch.full((1,), 0.5, dtype=torch.float32, device="cuda")
 word = torch.zeros(1, dtype=torch.float32, device="cuda")
+seed = torch.full((1,), 0x5EED, dtype=torch.int64, device="cuda")
 hook = ftar.bench_lib().ftar_debug_cast_variant
 hook.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                  ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
@@ -63,7 +68,7 @@ def make(label):
         total = int(base[5:]) << 20
         return (lambda i: ftar.reduce([bufs[i % S][0]], bufs[i % S][1], total // 2, "u8", "sum", stream=stream)), total
     pair, _, var = base.partition("@")
-    pair, plus, _ = pair.partition("+")
+    pair, plus, _ = pair.partition("+")   # _: "amax" or "sr"
     s, d = pair.split(">")
     n, total = moved(pair)
     if var:
@@ -74,6 +79,9 @@ def make(label):
                       scale.data_ptr(), stream.cuda_stream)
             assert st == 0, (label, st, ftar.last_error())
         return launch, total
+    if plus and _ == "sr":
+        return (lambda i: ftar.cast_scaled(bufs[i % S][0], bufs[i % S][1], n, s, d, scale=scale, stream=stream,
+                                           rounding="stochastic", seed=seed, offset=i * n)), total
     am = word if plus else None
     return (lambda i: ftar.cast_scaled(bufs[i % S][0], bufs[i % S][1], n, s, d, scale=scale, amax=am, stream=stream)), total
 
@@ -82,6 +90,8 @@ pairs = a.pairs.split(",")
 labels = list(pairs) + [pairs[0] + "#2"]
 if a.amax:
     labels += [p + "+amax" for p in pairs]
+sr_pairs = [p for p in pairs if p.split(">")[1] in F8] if a.sr else []
+labels += [p + "+sr" for p in sr_pairs]
 if a.layouts:
     labels += [f"{p}@{lay}.{u}" for p in a.layout_pairs.split(",") for lay, u in VARIANTS]
 for mib in sorted({moved(p)[1] >> 20 for p in pairs}):
@@ -107,3 +117,6 @@ for lb, ts in res.items():
         return round(total / ms / 1e6, 1)
     print(json.dumps({"label": lb, "MiB_moved": total >> 20, "ms_med": round(med, 4), "GBps_med": rate(med),
                       "GBps_slowest": rate(max(ts)), "GBps_fastest": rate(min(ts))}), flush=True)
+for p in sr_pairs:
+    print(json.dumps({"label": p + "+sr / " + p, "ratio_of_medians": round(statistics.median(res[p]) /
+                                                                          statistics.median(res[p + "+sr"]), 3)}), flush=True)
