@@ -269,6 +269,33 @@ ftar_status_t ftar_cast_scaled_sr(const void* src, ftar_dtype_t src_dtype, void*
                                      reinterpret_cast<unsigned*>(amax), static_cast<hipStream_t>(stream));
 }
 
+// The MX block-scaled casts (mx_kernels.hip): kernels only, so each call is the nodes of its kernels in a captured
+// graph.  The pair is checked first, then the mode and the headroom, then the pointers; count == 0 writes nothing.
+ftar_status_t ftar_mx_scales(const void* src, ftar_dtype_t src_dtype, ftar_dtype_t fp8_dtype, size_t count,
+                             int headroom, uint8_t* scales, void* stream) {
+  if (!ftar::mx_pair_supported(src_dtype, fp8_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (headroom < 0 || headroom > 31) return FTAR_ERR_INVALID_ARG;
+  if (count && (!src || !scales)) return FTAR_ERR_INVALID_ARG;
+  return ftar::launch_mx_scales(src, src_dtype, fp8_dtype, count, headroom, scales, static_cast<hipStream_t>(stream));
+}
+
+ftar_status_t ftar_mx_quantize(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                               size_t count, int mode, int headroom, uint8_t* scales, void* stream) {
+  if (!ftar::mx_pair_supported(src_dtype, dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (mode != FTAR_MX_COMPUTE && mode != FTAR_MX_GIVEN) return FTAR_ERR_INVALID_ARG;
+  if (headroom < 0 || headroom > 31 || (mode == FTAR_MX_GIVEN && headroom != 0)) return FTAR_ERR_INVALID_ARG;
+  if (count && (!src || !dst || !scales)) return FTAR_ERR_INVALID_ARG;
+  return ftar::launch_mx_quantize(src, src_dtype, dst, dst_dtype, count, mode == FTAR_MX_GIVEN, headroom, scales,
+                                  static_cast<hipStream_t>(stream));
+}
+
+ftar_status_t ftar_mx_dequantize(const void* src, ftar_dtype_t src_dtype, const uint8_t* scales, void* dst,
+                                 ftar_dtype_t dst_dtype, size_t count, void* stream) {
+  if (!ftar::mx_pair_supported(dst_dtype, src_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (count && (!src || !dst || !scales)) return FTAR_ERR_INVALID_ARG;
+  return ftar::launch_mx_dequantize(src, src_dtype, scales, dst, dst_dtype, count, static_cast<hipStream_t>(stream));
+}
+
 // get_stages (mpi_mod.hpp:1419-1486), minus its two bugs: an unset FT_TOPO
 // is reported (the reference exit(1)s for every P > 1) and a trailing comma
 // does not repeat the last width (the reference's `while(!ss.eof())` does).

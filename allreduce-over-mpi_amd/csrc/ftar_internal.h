@@ -254,6 +254,16 @@ bool cast_sr_pair_supported(ftar_dtype_t src, ftar_dtype_t dst);
 ftar_status_t launch_cast_scaled_sr(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt,
                                     size_t count, const float* scale, const unsigned long long* seed,
                                     unsigned long long offset, unsigned* amax, hipStream_t stream);
+// The MX block-scaled casts' kernels (mx_kernels.hip; the contract: include/ftar.h): one E8M0 byte per 32 elements.
+// wide in {f32, bf16, f16} with f8 in {e4m3, e5m2}; any other pair: FTAR_ERR_UNSUPPORTED before anything else.
+// Kernels only: no memset, no host read.  given: the quantize reads scales[] instead of writing it.
+bool mx_pair_supported(ftar_dtype_t wide, ftar_dtype_t f8);
+ftar_status_t launch_mx_scales(const void* src, ftar_dtype_t src_dt, ftar_dtype_t f8_dt, size_t count, int headroom,
+                               unsigned char* scales, hipStream_t stream);
+ftar_status_t launch_mx_quantize(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t f8_dt, size_t count,
+                                 bool given, int headroom, unsigned char* scales, hipStream_t stream);
+ftar_status_t launch_mx_dequantize(const void* src, ftar_dtype_t f8_dt, const unsigned char* scales, void* dst,
+                                   ftar_dtype_t dst_dt, size_t count, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // transports (transport_rccl.cpp, transport_local.cpp, transport_host.cpp; their IPC plumbing: ipc.cpp)

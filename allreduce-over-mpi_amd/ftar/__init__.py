@@ -131,6 +131,9 @@ _lib.ftar_reduce_amax.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, cty
                                   _int, _vp, _vp]
 _lib.ftar_cast_scaled.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, _vp]
 _lib.ftar_cast_scaled_sr.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, ctypes.c_uint64, _vp, _vp]
+_lib.ftar_mx_scales.argtypes = [_vp, _int, _int, _sz, _int, _vp, _vp]
+_lib.ftar_mx_quantize.argtypes = [_vp, _int, _vp, _int, _sz, _int, _int, _vp, _vp]
+_lib.ftar_mx_dequantize.argtypes = [_vp, _int, _vp, _vp, _int, _sz, _vp]
 _lib.ftar_topo_parse.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _int, ctypes.POINTER(Topo)]
 _lib.ftar_topo_from_env.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
 _lib.ftar_topo_choose.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
@@ -419,6 +422,79 @@ def cast_scaled_tensor(src, dst, scale=None, amax=None, stream=None, rounding="n
         _one_elem(seed, "seed", src.device, torch.int64)
     cast_scaled(src, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), scale, amax, stream, rounding,
                 seed if stochastic else None, offset)
+    return dst
+
+
+# ---- MX block-scaled casts wide <-> fp8 + one E8M0 scale byte per 32 elements ---------
+MX_BLOCK = 32                                   # FTAR_MX_BLOCK
+MX_MODE = {"compute": 0, "given": 1}            # ftar_mx_mode_t
+
+
+def mx_nblocks(n):
+    """The scale bytes of n elements: ceil(n / 32)."""
+    return (int(n) + MX_BLOCK - 1) // MX_BLOCK
+
+
+def _mx_mode(mode):
+    if mode not in MX_MODE:
+        raise ValueError(f"mode must be 'compute' or 'given', not {mode!r}")
+    return MX_MODE[mode]
+
+
+def mx_scales(src, scales, count, src_dtype, fp8_dtype, headroom=0, stream=None):
+    """scales[b] = the E8M0 byte of block b (32 elements) of an f32, bf16 or f16 src for the wire format fp8_dtype
+    (ftar_mx_scales): the smallest power of two at which the block's peak fits the format, `headroom` binades
+    (0..31) left free above it; 255 for a block with an inf or a NaN.  Writes mx_nblocks(count) bytes."""
+    _check(_lib.ftar_mx_scales(_ptr(src), _dt(src_dtype), _dt(fp8_dtype), count, int(headroom), _ptr(scales),
+                               _stream(stream)), "ftar_mx_scales")
+
+
+def mx_quantize(src, dst, scales, count, src_dtype, dst_dtype, mode="compute", headroom=0, stream=None):
+    """dst[i] = (src[i] as fp32 * 2^(127 - scales[i // 32])) rounded to the fp8 dst_dtype (ftar_mx_quantize), no
+    saturation.  mode="compute": one pass that writes scales (mx_scales' bytes) and dst; mode="given": reads
+    scales, device memory an earlier kernel on the stream may have written (headroom must be 0).  Any other mode
+    raises ValueError before any device work."""
+    _check(_lib.ftar_mx_quantize(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _mx_mode(mode),
+                                 int(headroom), _ptr(scales), _stream(stream)), "ftar_mx_quantize")
+
+
+def mx_dequantize(src, scales, dst, count, src_dtype, dst_dtype, stream=None):
+    """dst[i] = (src[i] as fp32 * 2^(scales[i // 32] - 127)) rounded to dst_dtype (ftar_mx_dequantize): fp8 to f32,
+    bf16 or f16; a block whose scale byte is 255 comes back all NaN."""
+    _check(_lib.ftar_mx_dequantize(_ptr(src), _dt(src_dtype), _ptr(scales), _ptr(dst), _dt(dst_dtype), count,
+                                   _stream(stream)), "ftar_mx_dequantize")
+
+
+def _mx_tensors(wide, f8, scales):
+    """The checks of the tensor forms: ValueError before any device work."""
+    import torch
+    if wide.numel() != f8.numel():
+        raise ValueError(f"the wide tensor has {wide.numel()} elements, the fp8 tensor {f8.numel()}")
+    if scales.dtype != torch.uint8:
+        raise ValueError(f"scales must be a torch.uint8 tensor, not {scales.dtype}")
+    if scales.numel() < mx_nblocks(wide.numel()):
+        raise ValueError(f"scales has {scales.numel()} bytes, {wide.numel()} elements need {mx_nblocks(wide.numel())}")
+    if not (wide.is_contiguous() and f8.is_contiguous() and scales.is_contiguous()):
+        raise ValueError("src, dst and scales must be contiguous")
+    if not (wide.device == f8.device == scales.device):
+        raise ValueError(f"src, dst and scales are on {wide.device}, {f8.device} and {scales.device}")
+
+
+def mx_quantize_tensor(src, dst, scales, mode="compute", headroom=0, stream=None):
+    """mx_quantize on tensors: src f32 / bf16 / f16, dst torch.float8_e4m3fn / torch.float8_e5m2 of equal numel,
+    scales torch.uint8 with at least mx_nblocks(src.numel()) elements.  ValueError unless all three are contiguous
+    and on one device and the mode is known.  Returns dst."""
+    _mx_mode(mode)
+    _mx_tensors(src, dst, scales)
+    mx_quantize(src, dst, scales, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), mode, headroom, stream)
+    return dst
+
+
+def mx_dequantize_tensor(src, scales, dst, stream=None):
+    """mx_dequantize on tensors (src an fp8 tensor, scales torch.uint8, dst f32 / bf16 / f16); the checks of
+    mx_quantize_tensor.  Returns dst."""
+    _mx_tensors(dst, src, scales)
+    mx_dequantize(src, scales, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), stream)
     return dst
 
 

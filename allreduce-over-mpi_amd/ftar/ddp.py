@@ -36,6 +36,9 @@ Values of the caller's own (a loss scale to agree on) still go through `comm.all
 fp8_compress_hook (with Fp8CompressState, at the end of this module) reduces the same buckets on an fp8 wire:
 quantize with a power-of-two scale (ftar_cast_scaled, or with rounding="stochastic" ftar_cast_scaled_sr), AllReduce
 with op="avg" and amax, dequantize; the scale follows the amax one step behind (next_fp8_scale), on the device.
+mx_compress_hook (with MxCompressState) is the block-scaled (MX) form of that wire: one power-of-two scale byte per
+32 elements, agreed among the ranks in the same step by a MAX AllReduce of the bytes, so small layers of a bucket
+keep their bits and no step overflows the wire; no scale policy to run.
 
 The reference reduces MPI buffers (MPI_Allreduce_FT, mpi_mod.hpp:1723-1778); a DDP bucket is the same call on
 a device tensor, in place (`sendbuf = MPI_IN_PLACE`).
@@ -263,6 +266,92 @@ def fp8_compress_hook(state, bucket):
     state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream, amax=a)
     ftar.cast_scaled(wire, t, n, f8, dt, scale=state.inv_scale, stream=stream)
     torch.maximum(state.amax, a, out=state.amax)
+    state.calls += 1
+    fut = torch.futures.Future(devices=[t.device])
+    fut.set_result(t)
+    return fut
+
+
+# ---- the MX (block-scaled) fp8 wire ---------------------------------------------------------------------
+class MxCompressState:
+    """What mx_compress_hook needs: the communicator, the wire format ("e4m3" or "e5m2"), optionally a fixed
+    topology, and `headroom` (0..31): the binades left free above each block's peak (ftar_mx_scales).  On the first
+    bucket's device it keeps a grow-only fp8 wire buffer, a grow-only uint8 scale buffer (one byte per 32 elements)
+    and a 1-element fp32 flag.  found_inf() is 1.0 once any reduced scale byte since reset() was 255 -- a block that
+    held an inf or a NaN on some rank -- and stays on the device.  There is no scale policy, no update_scale() and no
+    amax: every block's scale is computed from this step's data.  No host synchronisation anywhere."""
+
+    def __init__(self, comm, fmt="e4m3", topo=None, lonely=0, headroom=0):
+        if fmt not in FP8_MAX:
+            raise ValueError(f"fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
+        if isinstance(headroom, bool) or not isinstance(headroom, int) or not 0 <= headroom <= 31:
+            raise ValueError(f"headroom must be an integer in 0..31, not {headroom!r}")
+        self.comm, self.fmt, self.topo, self.lonely, self.headroom = comm, fmt, topo, lonely, headroom
+        self.wire_dtype = _FP8_DTYPE[fmt]
+        self._wire = self._scales = self._inf = None
+        self.calls = 0
+
+    def _on(self, device, n):
+        if self._inf is None:
+            self._inf = torch.zeros(1, dtype=torch.float32, device=device)
+        if self._wire is None or self._wire.numel() < n:
+            self._wire = torch.empty(n, dtype=torch.uint8, device=device)
+            self._scales = torch.empty(ftar.mx_nblocks(n), dtype=torch.uint8, device=device)
+        return self._wire, self._scales
+
+    def reset(self):
+        """Clear the flag (once per optimizer step, after the scaler has read found_inf())."""
+        if self._inf is not None:
+            self._inf.zero_()
+
+    def found_inf(self):
+        """A 1-element fp32 device tensor: 1.0 once a reduced scale byte since reset() was 255, else 0.0."""
+        if self._inf is None:
+            raise RuntimeError("found_inf() before the first bucket")
+        return self._inf
+
+
+def mx_compress_hook(state, bucket):
+    """DDP comm hook: an f32, bf16 or fp16 bucket reduced on an MX wire -- fp8 elements plus one E8M0 scale byte per
+    32 -- in five steps, all on the stream the backward pass runs on, no host synchronisation:
+    (1) ftar_mx_scales: each block's scale byte from this rank's bucket, state.headroom binades above its peak;
+    (2) the bytes' in-place AllReduce of u8 with op="max": every rank now holds each block's largest scale, and 255
+        (NaN) wherever any rank's block held an inf or a NaN -- a NaN byte wins the unsigned MAX by itself;
+    (3) ftar_mx_quantize with those given scales: two fp8 blocks that share a scale byte sum as plain fp8 values;
+    (4) the wire's in-place AllReduce with op="avg";
+    (5) ftar_mx_dequantize back into the bucket; a block whose byte is 255 comes back all NaN on every rank, and
+        state.found_inf() turns 1.0.
+    Returns a completed future, as allreduce_hook does.
+
+      * In the one-round forms (the default) the mean of P stored values, each at most the format's maximum, is
+        summed in fp32, scaled and rounded once: it cannot overflow at headroom=0.  That holds for a one-stage
+        topology ("P"); a multi-stage tree ("2,2") stores its inner nodes in fp8 in every form -- the one-round forms
+        reproduce the staged bits -- and two equal peaks under one inner node overflow it at headroom=0.
+      * The staged forms round partial sums to fp8 between hops, where a partial sum of up to P values must still fit:
+        they need headroom >= ceil(log2 P) (a tree in any form: log2 of the ranks under its largest inner node).
+      * The wire costs n + 2 * ceil(n / 32) bytes per rank (payload, and the scale bytes once in each AllReduce)
+        against 2n for bf16, and the hook reads the bucket twice (steps 1 and 3).
+
+    Prefer it to fp8_compress_hook when a bucket's layers differ by many binades (at one scale per bucket an e4m3
+    element under 2^-10 of the largest is stored as zero) or when a skipped step after an overflow is not acceptable;
+    fp8_compress_hook moves fewer bytes and reads the bucket once.
+    A bucket that is not float32, bfloat16 or float16, or not contiguous, raises ValueError before any device work."""
+    t = bucket.buffer()
+    if t.dtype not in _BUCKET_DTYPES:
+        raise ValueError(f"mx_compress_hook takes float32, bfloat16 or float16 buckets, not {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError("mx_compress_hook needs a contiguous bucket")
+    n = t.numel()
+    nb = ftar.mx_nblocks(n)
+    stream = torch.cuda.current_stream(t.device)
+    wire, scales = state._on(t.device, n)
+    dt, f8 = ftar._dt(str(t.dtype)), ftar._dt(state.wire_dtype)
+    ftar.mx_scales(t, scales, n, dt, f8, headroom=state.headroom, stream=stream)
+    state.comm.allreduce(None, scales, nb, "u8", "max", topo_=state.topo, lonely=state.lonely, stream=stream)
+    ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream)
+    state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream)
+    ftar.mx_dequantize(wire, scales, t, n, f8, dt, stream=stream)
+    torch.maximum(state._inf, (scales[:nb].max() == 255).to(torch.float32).reshape(1), out=state._inf)
     state.calls += 1
     fut = torch.futures.Future(devices=[t.device])
     fut.set_result(t)

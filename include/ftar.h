@@ -81,6 +81,7 @@ typedef enum {
  *   every other dtype (f64 included: its amax does not fit the word) and every other op is refused.
  *   cast (ftar_cast_scaled): f32 bf16 f16 -> f8e4m3 f8e5m2 and back, times a device scale; every other pair is refused.
  *   stochastic cast (ftar_cast_scaled_sr): f32 bf16 f16 -> f8e4m3 f8e5m2 only; the way back and every other pair is refused.
+ *   MX casts (ftar_mx_scales, ftar_mx_quantize: f32 bf16 f16 -> f8e4m3 f8e5m2; ftar_mx_dequantize: the way back); every other pair is refused.
  *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
  * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
@@ -186,6 +187,44 @@ typedef enum {
  * a NULL seed, a seed not 8-byte aligned, a scale or amax not 4-byte aligned, or a NULL src or dst with
  * count > 0 returns FTAR_ERR_INVALID_ARG; every refusal comes before any device work and leaves dst and *amax
  * untouched.  count == 0 succeeds, and a non-NULL amax then holds +0.0.
+ *
+ * MX block-scaled casts (ftar_mx_scales, ftar_mx_quantize, ftar_mx_dequantize): an fp8 wire with one power-of-two
+ * scale byte (OCP E8M0) per block of FTAR_MX_BLOCK = 32 elements.  Block b of a call covers the call's indices
+ * [32b, min(32b + 32, count)), counted from element 0 of that call; the last block may be partial;
+ * nblocks = ceil(count / 32).  A scale byte s means 2^(s - 127) for s in 0..254; s = 255 is NaN.  Wide dtypes are
+ * f32, bf16 and f16, fp8 dtypes f8e4m3 (emax = 8) and f8e5m2 (emax = 15): the 6 + 6 pairs of ftar_cast_scaled,
+ * every other pair refused as there (FTAR_ERR_UNSUPPORTED, that check first).  All in integers:
+ *   The block's scale (the "fit" rule).  a = the unsigned maximum over the block's own elements of
+ *   bits(widen(src[i])) & 0x7fffffff, the widening exact.  If a >= 0x7f800000 (an inf or a NaN in the block)
+ *   s = 255; otherwise
+ *     s = min(254, max(0, (a >> 23) - emax + (((a & 0x7fffff) > 0x600000) ? 1 : 0)) + headroom).
+ *   Both formats' largest finite value is 1.75 x 2^emax (448, 57344), so s is the smallest exponent at which the
+ *   block's largest magnitude times 2^(127 - s) is at most that value: the block's scaled peak lies in
+ *   (0.875 x 2^emax, 1.75 x 2^emax] x 2^-headroom unless s was clamped at 0 (stored, it may round down onto the
+ *   interval's lower end, which fp8 holds exactly), and no stored element of a finite
+ *   block is NaN or inf -- which matters because these casts do not saturate.  An all-zero block (-0 included)
+ *   gives s = headroom.  headroom (0..31) leaves that many binades free above the block's peak: the staged
+ *   AllReduce forms round partial sums to fp8 between hops and need it.  This is the ROUND-UP variant of the MX
+ *   scale: it differs from OCP's floor rule (s = floor(log2 peak) - emax) exactly in the blocks whose peak
+ *   mantissa exceeds 1.75, where OCP saturates the top eighth of the binade and this rule takes the next scale.
+ *   Quantize.  dst[i] = cvt_fp8(mul_rn_f32(widen(src[i]), q(s))), s the scale byte of i's block;
+ *   q(s) = 2^(127 - s): bits (254 - s) << 23 for s <= 253, 0x00400000 for s = 254; q(255) = 1.0f, so the payload of
+ *   a NaN block is the plain cast and the block is NaN through its scale.  The multiply and the narrowing are
+ *   ftar_cast_scaled's (subnormal products kept, RNE, no saturation): every block equals ftar_cast_scaled on that
+ *   block with r = q(s).  With given scales an element may exceed the format and becomes NaN (e4m3) / +-inf (e5m2).
+ *   Dequantize.  dst[i] = round_to_dst(mul_rn_f32(widen(src[i]), d(s))); d(s) has bits s << 23 for s in 1..254 and
+ *   0x00400000 for s = 0; for s = 255 every element of the block is a NaN of unspecified pattern.  An f32
+ *   destination holds the product itself; bf16 and f16 take the one RNE of ftar_cast_scaled's dequantizes (f16 may
+ *   overflow to +-inf).
+ * ftar_mx_quantize(FTAR_MX_COMPUTE) stores exactly what ftar_mx_scales followed by ftar_mx_quantize(FTAR_MX_GIVEN)
+ * stores.  After the pair check, FTAR_ERR_INVALID_ARG: a NULL src / dst / scales with count > 0, a mode outside the
+ * enum, a headroom outside 0..31, a headroom != 0 with FTAR_MX_GIVEN; every refusal comes before any device work
+ * and leaves every buffer untouched.  count == 0 succeeds and writes nothing.  Pointers need only their element's
+ * alignment and scales none: a call whose src and dst are both 16-byte aligned runs the vector kernels, any other
+ * an element-wise family (one block per lane) that stores the same bits.  Each call enqueues kernels only -- no
+ * memset, no host read, no synchronisation -- so it captures into a HIP graph and the scales may come from an
+ * earlier kernel on the stream.  Splitting [0, n) at a multiple of 32 into two calls stores the same bits.  src,
+ * dst and scales must not overlap.  MXFP6 / MXFP4 and stochastic rounding of the MX quantize are not covered.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
@@ -273,6 +312,19 @@ ftar_status_t ftar_cast_scaled(const void* src, ftar_dtype_t src_dtype, void* ds
 ftar_status_t ftar_cast_scaled_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
                                   size_t count, const float* scale, const uint64_t* seed, uint64_t offset,
                                   float* amax, void* stream);
+/* MX block-scaled casts (extension; the MX paragraph above): fp8 elements plus one E8M0 scale byte per 32. */
+#define FTAR_MX_BLOCK 32
+typedef enum { FTAR_MX_COMPUTE = 0, FTAR_MX_GIVEN = 1 } ftar_mx_mode_t;
+/* scales[b], b < ceil(count / 32), of a wide src for the fp8 format fp8_dtype: reads src once, writes nblocks bytes. */
+ftar_status_t ftar_mx_scales(const void* src, ftar_dtype_t src_dtype, ftar_dtype_t fp8_dtype, size_t count,
+                             int headroom, uint8_t* scales, void* stream);
+/* FTAR_MX_COMPUTE: one pass over src that writes scales[] and dst[]; FTAR_MX_GIVEN: reads scales[] (device memory,
+ * possibly written by an earlier kernel on the stream; headroom must be 0) and writes dst[]. */
+ftar_status_t ftar_mx_quantize(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                               size_t count, int mode, int headroom, uint8_t* scales, void* stream);
+/* dst[i] = round_to_dst(fp32(src[i]) x 2^(scales[i / 32] - 127)), src fp8, dst f32 / bf16 / f16. */
+ftar_status_t ftar_mx_dequantize(const void* src, ftar_dtype_t src_dtype, const uint8_t* scales, void* dst,
+                                 ftar_dtype_t dst_dtype, size_t count, void* stream);
 
 /* ---- topology ------------------------------------------------------------
  * ftar_topo_parse: FT_TOPO / FT_LONELY strings (NULL = unset) for nranks.
