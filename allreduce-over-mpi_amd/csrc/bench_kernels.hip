@@ -16,122 +16,122 @@ namespace ftar {
 namespace {
 // progressive LDS-staged kernel: (tiles per wave U, waves per workgroup W)
 template <class Tr, int K>
-hipError_t variant_prog(int v, const void* const* srcs, void* dst, size_t nvec, hipStream_t s) {
+hipError_t variant_prog(int v, const Launch& c, const Split16& sp) {
   switch (v) {
-    case 40: return launch_lds<Tr, K, 4, 4>(srcs, dst, nvec, s);
-    case 41: return launch_lds<Tr, K, 3, 4>(srcs, dst, nvec, s);
-    case 42: return launch_lds<Tr, K, 2, 4>(srcs, dst, nvec, s);
-    case 43: return launch_lds<Tr, K, 4, 2>(srcs, dst, nvec, s);
-    case 44: return launch_lds<Tr, K, 3, 6>(srcs, dst, nvec, s);
-    case 45: return launch_lds<Tr, K, 2, 6>(srcs, dst, nvec, s);
-    case 46: return launch_lds<Tr, K, 2, 8>(srcs, dst, nvec, s);
-    case 47: return launch_lds<Tr, K, 1, 8>(srcs, dst, nvec, s);
-    case 48: return launch_lds<Tr, K, 3, 2>(srcs, dst, nvec, s);
-    case 49: return launch_lds<Tr, K, 6, 2>(srcs, dst, nvec, s);
-    case 50: return launch_lds<Tr, K, 2, 2>(srcs, dst, nvec, s);
-    case 51: return launch_lds<Tr, K, 1, 4>(srcs, dst, nvec, s);
-    case 52: return launch_lds<Tr, K, 5, 2>(srcs, dst, nvec, s);
-    case 53: return launch_lds<Tr, K, 2, 5>(srcs, dst, nvec, s);
+    case 40: return launch_lds<Tr, K, 4, 4>(c, sp);
+    case 41: return launch_lds<Tr, K, 3, 4>(c, sp);
+    case 42: return launch_lds<Tr, K, 2, 4>(c, sp);
+    case 43: return launch_lds<Tr, K, 4, 2>(c, sp);
+    case 44: return launch_lds<Tr, K, 3, 6>(c, sp);
+    case 45: return launch_lds<Tr, K, 2, 6>(c, sp);
+    case 46: return launch_lds<Tr, K, 2, 8>(c, sp);
+    case 47: return launch_lds<Tr, K, 1, 8>(c, sp);
+    case 48: return launch_lds<Tr, K, 3, 2>(c, sp);
+    case 49: return launch_lds<Tr, K, 6, 2>(c, sp);
+    case 50: return launch_lds<Tr, K, 2, 2>(c, sp);
+    case 51: return launch_lds<Tr, K, 1, 4>(c, sp);
+    case 52: return launch_lds<Tr, K, 5, 2>(c, sp);
+    case 53: return launch_lds<Tr, K, 2, 5>(c, sp);
     // small workgroups, many per CU (round 2: tools/kexp/k8_exp.hip found U1 W2 / U2 W1 ahead at k = 2..9)
-    case 54: return launch_lds<Tr, K, 1, 2>(srcs, dst, nvec, s);
-    case 55: return launch_lds<Tr, K, 1, 1>(srcs, dst, nvec, s);
-    case 56: return launch_lds<Tr, K, 2, 1>(srcs, dst, nvec, s);
-    case 57: return launch_lds<Tr, K, 1, 3>(srcs, dst, nvec, s);
-    case 58: return launch_lds<Tr, K, 3, 1>(srcs, dst, nvec, s);
-    case 59: return launch_lds<Tr, K, 4, 1>(srcs, dst, nvec, s);
+    case 54: return launch_lds<Tr, K, 1, 2>(c, sp);
+    case 55: return launch_lds<Tr, K, 1, 1>(c, sp);
+    case 56: return launch_lds<Tr, K, 2, 1>(c, sp);
+    case 57: return launch_lds<Tr, K, 1, 3>(c, sp);
+    case 58: return launch_lds<Tr, K, 3, 1>(c, sp);
+    case 59: return launch_lds<Tr, K, 4, 1>(c, sp);
     // load cache policy (the aux operand of global_load_lds) at the production shape: 2 = nt (production)
-    case 60: return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 1>(srcs, dst, nvec, s);
-    case 61: return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 3>(srcs, dst, nvec, s);
-    case 62: return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 2>(srcs, dst, nvec, s);
+    case 60: return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 1>(c, sp);
+    case 61: return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 3>(c, sp);
+    case 62: return launch_lds<Tr, K, kLdsTiles<Tr, K>, kLdsWaves<Tr, K>, 2>(c, sp);
   }
   return hipErrorInvalidValue;
 }
 template <class Tr, int K>
-hipError_t variant_k(int v, const void* const* srcs, int k, void* dst, size_t nvec, hipStream_t s) {
+hipError_t variant_k(int v, const Launch& c, const Split16& sp) {
   switch (v) {
-    case 0: return launch_cfg<Tr, K, 2, true, false, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 1: return launch_cfg<Tr, K, 1, true, false, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 2: return launch_cfg<Tr, K, 4, true, false, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 3: return launch_cfg<Tr, K, 1, true, false, 512>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 4: return launch_cfg<Tr, K, 2, true, false, 512>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 5: return launch_cfg<Tr, K, 1, true, false, 1024>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 6: return launch_cfg<Tr, K, 2, true, false, 128>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 7: return launch_cfg<Tr, K, 2, false, false, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 8: return launch_cfg<Tr, K, 1, true, false, 256>(srcs, k, dst, nvec, 0, 0, s, 2048);
-    case 9: return launch_cfg<Tr, K, 2, true, false, 256>(srcs, k, dst, nvec, 0, 0, s, 4096);
-    case 10: return launch_cfg<Tr, K, 1, true, false, 128>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 11: return launch_cfg<Tr, K, 4, true, false, 128>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 12: return launch_cfg<Tr, K, 2, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);   // nt stores
-    case 13: return launch_cfg<Tr, K, 1, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 14: return launch_cfg<Tr, K, 4, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 15: return launch_cfg<Tr, K, 2, false, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 16: return launch_cfg<Tr, K, 2, true, true, 512>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 17: return launch_cfg<Tr, K, 4, true, false, 256>(srcs, k, dst, nvec, 0, 0, s, 4096);
-    case 18: return launch_cfg<Tr, K, 2, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 8192);
-    case 19: return launch_cfg<Tr, K, 4, true, true, 512>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 23: return launch_cfg<Tr, K, 4, true, true, 128>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 24: return launch_cfg<Tr, K, 8, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 25: return launch_cfg<Tr, K, 2, true, true, 128>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 26: return launch_cfg<Tr, K, 1, true, true, 512>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 31: return launch_lds<Tr, K, (K <= 4 ? 4 : 2), 4, 2, false>(srcs, dst, nvec, s);
-    case 32: return launch_lds<Tr, K, (K <= 4 ? 4 : (K <= 6 ? 3 : 2)), 4, 2, false>(srcs, dst, nvec, s);
-    case 33: return launch_lds<Tr, K, 1, 4, 2, false>(srcs, dst, nvec, s);
-    case 27: return launch_cfg<Tr, 0, 2, true, true, 512>(srcs, k, dst, nvec, 0, 0, s, 0);  // runtime-k loop
-    case 28: return launch_cfg<Tr, 0, 4, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 29: return launch_cfg<Tr, 0, 1, true, true, 512>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 30: return launch_cfg<Tr, 0, 2, true, true, 256>(srcs, k, dst, nvec, 0, 0, s, 0);
-    case 20: return launch_lds<Tr, K, 2, 4, 2, false>(srcs, dst, nvec, s);  // LDS-DMA, nt, wait for all
-    case 21: return launch_lds<Tr, K, 4, 4, 2, false>(srcs, dst, nvec, s);
-    case 22: return launch_lds<Tr, K, 2, 4, 0, false>(srcs, dst, nvec, s);  // LDS-DMA, default policy
+    case 0: return launch_cfg<Tr, K, 2, true, false, 256>(c, sp);
+    case 1: return launch_cfg<Tr, K, 1, true, false, 256>(c, sp);
+    case 2: return launch_cfg<Tr, K, 4, true, false, 256>(c, sp);
+    case 3: return launch_cfg<Tr, K, 1, true, false, 512>(c, sp);
+    case 4: return launch_cfg<Tr, K, 2, true, false, 512>(c, sp);
+    case 5: return launch_cfg<Tr, K, 1, true, false, 1024>(c, sp);
+    case 6: return launch_cfg<Tr, K, 2, true, false, 128>(c, sp);
+    case 7: return launch_cfg<Tr, K, 2, false, false, 256>(c, sp);
+    case 8: return launch_cfg<Tr, K, 1, true, false, 256>(c, sp, 2048);
+    case 9: return launch_cfg<Tr, K, 2, true, false, 256>(c, sp, 4096);
+    case 10: return launch_cfg<Tr, K, 1, true, false, 128>(c, sp);
+    case 11: return launch_cfg<Tr, K, 4, true, false, 128>(c, sp);
+    case 12: return launch_cfg<Tr, K, 2, true, true, 256>(c, sp);   // nt stores
+    case 13: return launch_cfg<Tr, K, 1, true, true, 256>(c, sp);
+    case 14: return launch_cfg<Tr, K, 4, true, true, 256>(c, sp);
+    case 15: return launch_cfg<Tr, K, 2, false, true, 256>(c, sp);
+    case 16: return launch_cfg<Tr, K, 2, true, true, 512>(c, sp);
+    case 17: return launch_cfg<Tr, K, 4, true, false, 256>(c, sp, 4096);
+    case 18: return launch_cfg<Tr, K, 2, true, true, 256>(c, sp, 8192);
+    case 19: return launch_cfg<Tr, K, 4, true, true, 512>(c, sp);
+    case 23: return launch_cfg<Tr, K, 4, true, true, 128>(c, sp);
+    case 24: return launch_cfg<Tr, K, 8, true, true, 256>(c, sp);
+    case 25: return launch_cfg<Tr, K, 2, true, true, 128>(c, sp);
+    case 26: return launch_cfg<Tr, K, 1, true, true, 512>(c, sp);
+    case 31: return launch_lds<Tr, K, (K <= 4 ? 4 : 2), 4, 2, false>(c, sp);
+    case 32: return launch_lds<Tr, K, (K <= 4 ? 4 : (K <= 6 ? 3 : 2)), 4, 2, false>(c, sp);
+    case 33: return launch_lds<Tr, K, 1, 4, 2, false>(c, sp);
+    case 27: return launch_cfg<Tr, 0, 2, true, true, 512>(c, sp);  // runtime-k loop
+    case 28: return launch_cfg<Tr, 0, 4, true, true, 256>(c, sp);
+    case 29: return launch_cfg<Tr, 0, 1, true, true, 512>(c, sp);
+    case 30: return launch_cfg<Tr, 0, 2, true, true, 256>(c, sp);
+    case 20: return launch_lds<Tr, K, 2, 4, 2, false>(c, sp);  // LDS-DMA, nt, wait for all
+    case 21: return launch_lds<Tr, K, 4, 4, 2, false>(c, sp);
+    case 22: return launch_lds<Tr, K, 2, 4, 0, false>(c, sp);  // LDS-DMA, default policy
   }
-  return variant_prog<Tr, K>(v, srcs, dst, nvec, s);
+  return variant_prog<Tr, K>(v, c, sp);
 }
 // k = 1 (a copy, vector_add/reduce_sum.h:36-47): variant 90 = production (the streaming copy kernel,
 // launch_gather), 40-62 = the LDS-DMA-staged kernel with K = 1 (load to LDS, store from LDS)
 template <class Tr>
-hipError_t variant_copy(int v, const void* const* srcs, void* dst, size_t nvec, hipStream_t s) {
+hipError_t variant_copy(int v, const Launch& c, const Split16& sp) {
   if (v == 90) {
-    const Segment seg{srcs[0], dst, nvec * 16};
-    return launch_gather(&seg, 1, s) == FTAR_SUCCESS ? hipSuccess : hipErrorInvalidValue;
+    const Segment seg{c.srcs[0], c.dst, sp.nvec * 16};
+    return launch_gather(&seg, 1, c.s) == FTAR_SUCCESS ? hipSuccess : hipErrorInvalidValue;
   }
-  return variant_prog<Tr, 1>(v, srcs, dst, nvec, s);
+  return variant_prog<Tr, 1>(v, c, sp);
 }
 
 template <class Tr>
-hipError_t variant_tr(int v, const void* const* srcs, int k, void* dst, size_t nvec, hipStream_t s) {
-  switch (k) {
-    case 1: return variant_copy<Tr>(v, srcs, dst, nvec, s);
-    case 2: return variant_k<Tr, 2>(v, srcs, k, dst, nvec, s);
-    case 3: return variant_k<Tr, 3>(v, srcs, k, dst, nvec, s);
-    case 4: return variant_k<Tr, 4>(v, srcs, k, dst, nvec, s);
-    case 5: return variant_prog<Tr, 5>(v, srcs, dst, nvec, s);
-    case 6: return variant_k<Tr, 6>(v, srcs, k, dst, nvec, s);
-    case 7: return variant_prog<Tr, 7>(v, srcs, dst, nvec, s);
-    case 8: return variant_k<Tr, 8>(v, srcs, k, dst, nvec, s);
-    case 10: return variant_prog<Tr, 10>(v, srcs, dst, nvec, s);
-    case 12: return variant_prog<Tr, 12>(v, srcs, dst, nvec, s);
-    case 16: return variant_prog<Tr, 16>(v, srcs, dst, nvec, s);
+hipError_t variant_tr(int v, const Launch& c, const Split16& sp) {
+  switch (c.k) {
+    case 1: return variant_copy<Tr>(v, c, sp);
+    case 2: return variant_k<Tr, 2>(v, c, sp);
+    case 3: return variant_k<Tr, 3>(v, c, sp);
+    case 4: return variant_k<Tr, 4>(v, c, sp);
+    case 5: return variant_prog<Tr, 5>(v, c, sp);
+    case 6: return variant_k<Tr, 6>(v, c, sp);
+    case 7: return variant_prog<Tr, 7>(v, c, sp);
+    case 8: return variant_k<Tr, 8>(v, c, sp);
+    case 10: return variant_prog<Tr, 10>(v, c, sp);
+    case 12: return variant_prog<Tr, 12>(v, c, sp);
+    case 16: return variant_prog<Tr, 16>(v, c, sp);
   }
   return hipErrorInvalidValue;
 }
 }  // namespace
 
-hipError_t hop_variant(int v, const void* const* srcs, int k, void* dst, size_t nvec, hipStream_t s) {
-  switch (k) {
-    case 2: return variant_prog<BF16SumHop, 2>(v, srcs, dst, nvec, s);
-    case 4: return variant_prog<BF16SumHop, 4>(v, srcs, dst, nvec, s);
-    case 8: return variant_prog<BF16SumHop, 8>(v, srcs, dst, nvec, s);
-    case 16: return variant_prog<BF16SumHop, 16>(v, srcs, dst, nvec, s);
+hipError_t hop_variant(int v, const Launch& c, const Split16& sp) {
+  switch (c.k) {
+    case 2: return variant_prog<BF16SumHop, 2>(v, c, sp);
+    case 4: return variant_prog<BF16SumHop, 4>(v, c, sp);
+    case 8: return variant_prog<BF16SumHop, 8>(v, c, sp);
+    case 16: return variant_prog<BF16SumHop, 16>(v, c, sp);
   }
   return hipErrorInvalidValue;
 }
 
 // the fp8 A/B (profiles/f8/): the (U, W) shapes 40-62 at k = 2 and 8 for one fp8 trait
 template <class Tr>
-hipError_t f8_variant(int v, const void* const* srcs, int k, void* dst, size_t nvec, hipStream_t s) {
-  switch (k) {
-    case 2: return variant_prog<Tr, 2>(v, srcs, dst, nvec, s);
-    case 8: return variant_prog<Tr, 8>(v, srcs, dst, nvec, s);
+hipError_t f8_variant(int v, const Launch& c, const Split16& sp) {
+  switch (c.k) {
+    case 2: return variant_prog<Tr, 2>(v, c, sp);
+    case 8: return variant_prog<Tr, 8>(v, c, sp);
   }
   return hipErrorInvalidValue;
 }
@@ -141,16 +141,17 @@ hipError_t f8_variant(int v, const void* const* srcs, int k, void* dst, size_t n
 extern "C" ftar_status_t ftar_debug_reduce_variant(int variant, int dtype, const void* const* srcs, int k, void* dst,
                                                    size_t count, void* stream) {
   if (reinterpret_cast<uintptr_t>(dst) & 15) return FTAR_ERR_INVALID_ARG;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  const ftar::Launch c{srcs, k, dst, static_cast<hipStream_t>(stream)};
+  auto vecs = [&](size_t per) { return ftar::Split16{true, 0, 0, count / per}; };  // whole vectors, aligned: no head or tail
   hipError_t e;
-  if (dtype == FTAR_FLOAT32 && count % 4 == 0) e = ftar::variant_tr<ftar::F32Sum>(variant, srcs, k, dst, count / 4, s);
+  if (dtype == FTAR_FLOAT32 && count % 4 == 0) e = ftar::variant_tr<ftar::F32Sum>(variant, c, vecs(4));
   else if (dtype == FTAR_BFLOAT16 && count % 8 == 0)
-    e = ftar::variant_tr<ftar::BF16Sum>(variant, srcs, k, dst, count / 8, s);
+    e = ftar::variant_tr<ftar::BF16Sum>(variant, c, vecs(8));
   // 100 + bf16: the ring's hop fold (rounds after every add), production shape (variant 62), k = 2, 4, 8, 16.
   // (The round-2 A/B of the two bf16 conversions, profiles/r02/s4/kbench_bf16_cvt.log, also built
   // 200 + bf16 / 300 + bf16 for the flat and hop folds with the integer RNE; dropped to keep build time.)
   else if (dtype == 100 + FTAR_BFLOAT16 && count % 8 == 0)
-    e = ftar::hop_variant(variant, srcs, k, dst, count / 8, s);
+    e = ftar::hop_variant(variant, c, vecs(8));
   // (The A/B of the 2-byte MAX traits, profiles/f16_minmax/kbench_2byte_max.log, also built the shape sweep
   // (variants 40-62, k = 2 and 8) for fp16 SUM, u16 SUM, 200 + f16 / 200 + i16 = MAX, and 300 + f16 = fp16 MAX by
   // integer keys (sign-magnitude flipped to two's complement per packed half, v_pk_max_i16, NaN lanes collected
@@ -158,11 +159,11 @@ extern "C" ftar_status_t ftar_debug_reduce_variant(int variant, int dtype, const
   // e4m3 (e5m2 runs the same instructions under other opcodes): the SUM, 200 + e4m3 = MAX as production does it
   // (widen, fp32 maximum, narrow), 300 + e4m3 = MAX by integer keys on the bytes (F8KeyMinMax); k = 2 and 8
   else if (dtype == FTAR_FLOAT8_E4M3 && count % 16 == 0)
-    e = ftar::f8_variant<ftar::E4M3Sum>(variant, srcs, k, dst, count / 16, s);
+    e = ftar::f8_variant<ftar::E4M3Sum>(variant, c, vecs(16));
   else if (dtype == 200 + FTAR_FLOAT8_E4M3 && count % 16 == 0)
-    e = ftar::f8_variant<ftar::F8MinMax<ftar::E4M3Fmt, true>>(variant, srcs, k, dst, count / 16, s);
+    e = ftar::f8_variant<ftar::F8MinMax<ftar::E4M3Fmt, true>>(variant, c, vecs(16));
   else if (dtype == 300 + FTAR_FLOAT8_E4M3 && count % 16 == 0)
-    e = ftar::f8_variant<ftar::F8KeyMinMax<false, true>>(variant, srcs, k, dst, count / 16, s);
+    e = ftar::f8_variant<ftar::F8KeyMinMax<false, true>>(variant, c, vecs(16));
   else return FTAR_ERR_INVALID_ARG;
   return e == hipSuccess ? FTAR_SUCCESS : FTAR_ERR_HIP;
 }
@@ -171,27 +172,32 @@ extern "C" ftar_status_t ftar_debug_reduce_variant(int variant, int dtype, const
 // register kernel of round 1 (tools/kbench_cold.py --shapes).
 extern "C" ftar_status_t ftar_debug_reduce_nested_lds(int lds, const void* const* srcs, int k, void* dst, size_t count,
                                                       int dtype, const int* shape, int nlevels, void* stream) {
-  return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, FTAR_SUM, static_cast<hipStream_t>(stream),
-                             false, shape, nlevels, lds != 0);
+  ftar::FoldCall f;
+  f.srcs = srcs; f.k = k; f.dst = dst; f.count = count; f.dt = (ftar_dtype_t)dtype;
+  f.stream = static_cast<hipStream_t>(stream);
+  f.shape = shape; f.nlevels = nlevels; f.lds = lds != 0;
+  return ftar::launch_reduce(f);
 }
 
 // Test hooks of the kernel-edge tests (tests/kernel_edges.py): the product's own launchers with every argument
-// the engine can give them.  ftar_debug_reduce_ex is launch_reduce unchanged but for amax (round_each: the hop folds;
-// lds = 0: the peer forms' ":vec" dispatch and the register tree kernels; scale may be NULL).
-extern "C" ftar_status_t ftar_debug_reduce_ex(const void* const* srcs, int k, void* dst, size_t count, int dtype, int op,
-                                              int round_each, const int* shape, int nlevels, int lds,
-                                              const double* scale, void* stream) {
-  return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, (ftar_op_t)op, static_cast<hipStream_t>(stream),
-                             round_each != 0, shape, nlevels, lds != 0, scale);
-}
-// The same with an amax word: every argument goes to launch_reduce unchanged (which refuses an amax without a
-// scale).  The word is NOT zeroed here: what it holds before the launch is the caller's to decide, as it is the
-// engine's, whose pieces max into one word launch after launch.
+// the engine can give them, each passed to launch_reduce unchanged (round_each: the hop folds; lds = 0: the peer
+// forms' ":vec" dispatch and the register tree kernels; scale may be NULL, and launch_reduce refuses an amax
+// without one).  The amax word is NOT zeroed here: what it holds before the launch is the caller's to decide, as
+// it is the engine's, whose pieces max into one word launch after launch.
 extern "C" ftar_status_t ftar_debug_reduce_amax_ex(const void* const* srcs, int k, void* dst, size_t count, int dtype,
                                                    int op, int round_each, const int* shape, int nlevels, int lds,
                                                    const double* scale, unsigned* amax, void* stream) {
-  return ftar::launch_reduce(srcs, k, dst, count, (ftar_dtype_t)dtype, (ftar_op_t)op, static_cast<hipStream_t>(stream),
-                             round_each != 0, shape, nlevels, lds != 0, scale, amax);
+  ftar::FoldCall f;
+  f.srcs = srcs; f.k = k; f.dst = dst; f.count = count; f.dt = (ftar_dtype_t)dtype;
+  f.op = (ftar_op_t)op; f.stream = static_cast<hipStream_t>(stream); f.round_each = round_each != 0;
+  f.shape = shape; f.nlevels = nlevels; f.lds = lds != 0; f.scale = scale; f.amax = amax;
+  return ftar::launch_reduce(f);
+}
+// The same without an amax word.
+extern "C" ftar_status_t ftar_debug_reduce_ex(const void* const* srcs, int k, void* dst, size_t count, int dtype, int op,
+                                              int round_each, const int* shape, int nlevels, int lds,
+                                              const double* scale, void* stream) {
+  return ftar_debug_reduce_amax_ex(srcs, k, dst, count, dtype, op, round_each, shape, nlevels, lds, scale, nullptr, stream);
 }
 
 // launch_gather on dsts[i][0..bytes[i]) = srcs[i][0..bytes[i]), i < nsegs (zero-byte segments included: the

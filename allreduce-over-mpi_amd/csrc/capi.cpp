@@ -200,14 +200,19 @@ size_t ftar_dtype_size(ftar_dtype_t dt) { return ftar::dtype_size(dt); }
 
 ftar_status_t ftar_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype, ftar_op_t op,
                           void* stream) {
-  return ftar::launch_reduce(srcs, k, dst, count, dtype, op, static_cast<hipStream_t>(stream));
+  ftar::FoldCall f;
+  f.srcs = srcs; f.k = k; f.dst = dst; f.count = count; f.dt = dtype;
+  f.op = op; f.stream = static_cast<hipStream_t>(stream);
+  return ftar::launch_reduce(f);
 }
 
 ftar_status_t ftar_reduce_nested(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
                                  ftar_op_t op, const int* shape, int nlevels, void* stream) {
   FTAR_RETURN_IF(ftar::check_fold_shape(shape, nlevels, k));  // for every dtype (only float sums use it)
-  return ftar::launch_reduce(srcs, k, dst, count, dtype, op, static_cast<hipStream_t>(stream), false, shape,
-                             nlevels);
+  ftar::FoldCall f;
+  f.srcs = srcs; f.k = k; f.dst = dst; f.count = count; f.dt = dtype;
+  f.op = op; f.stream = static_cast<hipStream_t>(stream); f.shape = shape; f.nlevels = nlevels;
+  return ftar::launch_reduce(f);
 }
 
 ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dtype,
@@ -217,8 +222,10 @@ ftar_status_t ftar_reduce_scaled(const void* const* srcs, int k, void* dst, size
   FTAR_RETURN_IF(ftar::check_fold_shape(shape, nlevels, k));
   // the kernels multiply by the scale as a float (f64: as it is); the cast happens at the launch
   const double r = dtype == FTAR_FLOAT64 ? scale : (double)(float)scale;
-  return ftar::launch_reduce(srcs, k, dst, count, dtype, FTAR_SUM, static_cast<hipStream_t>(stream), false, shape,
-                             nlevels, true, &r);
+  ftar::FoldCall f;
+  f.srcs = srcs; f.k = k; f.dst = dst; f.count = count; f.dt = dtype;
+  f.stream = static_cast<hipStream_t>(stream); f.shape = shape; f.nlevels = nlevels; f.scale = &r;
+  return ftar::launch_reduce(f);
 }
 
 // ftar_reduce_scaled and the amax of what it stored: a 4-byte memset of the word, then the one kernel, whose
@@ -235,8 +242,11 @@ ftar_status_t ftar_reduce_amax(const void* const* srcs, int k, void* dst, size_t
   const double r = (double)(float)scale;
   FTAR_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(float), static_cast<hipStream_t>(stream)));
   if (count == 0) return FTAR_SUCCESS;
-  return ftar::launch_reduce(srcs, k, dst, count, dtype, FTAR_SUM, static_cast<hipStream_t>(stream), false, shape,
-                             nlevels, true, &r, reinterpret_cast<unsigned*>(amax));
+  ftar::FoldCall f;
+  f.srcs = srcs; f.k = k; f.dst = dst; f.count = count; f.dt = dtype;
+  f.stream = static_cast<hipStream_t>(stream); f.shape = shape; f.nlevels = nlevels;
+  f.scale = &r; f.amax = reinterpret_cast<unsigned*>(amax);
+  return ftar::launch_reduce(f);
 }
 
 // The scaled cast wide <-> fp8 (cast_kernels.hip): with amax the same two nodes as ftar_reduce_amax, a 4-byte

@@ -588,9 +588,10 @@ ftar_status_t allreduce_locked(const void* sendbuf, void* recvbuf, size_t count,
   if (c->nranks == 1 && c->amax_cur) {  // an amax call: the copy becomes a k = 1 amax fold (in place without sendbuf)
     const void* src = sendbuf ? sendbuf : recvbuf;
     const double one = 1.0;  // AVG of one rank: r = 1
-    return count ? launch_reduce(&src, 1, recvbuf, count, dt, FTAR_SUM, stream, false, nullptr, 0, true, &one,
-                                 c->amax_cur)
-                 : FTAR_SUCCESS;
+    FoldCall f;
+    f.srcs = &src; f.k = 1; f.dst = recvbuf; f.count = count; f.dt = dt;
+    f.stream = stream; f.scale = &one; f.amax = c->amax_cur;
+    return count ? launch_reduce(f) : FTAR_SUCCESS;
   }
   if (c->nranks == 1) {  // mpi_mod.hpp:1739-1746
     if (sendbuf && count && host)
@@ -792,11 +793,14 @@ ftar_status_t allreduce_amax(const void* sendbuf, void* recvbuf, size_t count, f
     return st;
   }
   std::vector<const void*> srcs;
+  FoldCall f;
+  f.dst = amax; f.count = 1; f.dt = FTAR_INT32; f.op = FTAR_MAX; f.stream = stream;
   for (size_t lo = 0; lo < P; lo += FTAR_MAX_K - 1) {  // (more ranks than one fold has sources: in turns)
     srcs.clear();
     if (lo) srcs.push_back(amax);
     for (size_t j = lo; j < std::min(P, lo + FTAR_MAX_K - 1); ++j) srcs.push_back(slots + j);
-    FTAR_RETURN_IF(launch_reduce(srcs.data(), (int)srcs.size(), amax, 1, FTAR_INT32, FTAR_MAX, stream));
+    f.srcs = srcs.data(); f.k = (int)srcs.size();
+    FTAR_RETURN_IF(launch_reduce(f));
   }
   return done();
 }

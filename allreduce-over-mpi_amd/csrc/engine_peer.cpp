@@ -141,8 +141,12 @@ ftar_status_t peer_fold(const ReduceItem& r, const Plan& plan, ftar_dtype_t dt, 
   if (lo >= r.len) return FTAR_SUCCESS;
   // AVG: SUM, scaled on the root item (every piece of it); an amax call: the root item maxes into its word too
   const FoldOp fo = fold_op(op, dt, plan.nranks, amax);
-  return launch_reduce(srcs.data(), (int)srcs.size(), dst, std::min(len, r.len - lo), dt, fo.op, s, r.round_each,
-                       r.shape.data(), (int)r.shape.size(), lds, fo.scale(r.root), fo.amax(r.root));
+  FoldCall f;
+  f.srcs = srcs.data(); f.k = (int)srcs.size(); f.dst = dst; f.count = std::min(len, r.len - lo); f.dt = dt;
+  f.op = fo.op; f.stream = s; f.round_each = r.round_each;
+  f.shape = r.shape.data(); f.nlevels = (int)r.shape.size(); f.lds = lds;
+  f.scale = fo.scale(r.root); f.amax = fo.amax(r.root);
+  return launch_reduce(f);
 }
 
 namespace {

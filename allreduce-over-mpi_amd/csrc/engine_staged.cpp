@@ -231,9 +231,12 @@ ftar_status_t staged_allreduce(const void* sendbuf, void* recvbuf, size_t count,
         if (r.len <= lo) continue;
         srcs.clear();
         for (const Operand& o : r.srcs) srcs.push_back(sbuf(o.buf, o.off + lo, s));
-        FTAR_RETURN_IF(launch_reduce(srcs.data(), (int)srcs.size(), bufs[BUF_DST] + (r.off + lo) * esz,
-                                     std::min(chunk, r.len - lo), dt, fo.op, c->red_s, r.round_each, r.shape.data(),
-                                     (int)r.shape.size(), true, fo.scale(r.root), fo.amax(r.root)));
+        FoldCall f;
+        f.srcs = srcs.data(); f.k = (int)srcs.size(); f.dst = bufs[BUF_DST] + (r.off + lo) * esz;
+        f.count = std::min(chunk, r.len - lo); f.dt = dt; f.op = fo.op; f.stream = c->red_s;
+        f.round_each = r.round_each; f.shape = r.shape.data(); f.nlevels = (int)r.shape.size();
+        f.scale = fo.scale(r.root); f.amax = fo.amax(r.root);
+        FTAR_RETURN_IF(launch_reduce(f));
       }
       FTAR_CHECK_HIP(hipEventRecord(ev_r(s, k), c->red_s));
     }

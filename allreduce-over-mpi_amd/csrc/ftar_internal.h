@@ -157,26 +157,39 @@ ftar_status_t check_world(const Topology& t, int nranks, size_t count, Form form
 // ---------------------------------------------------------------------------
 // reduce kernels (reduce_impl.h; dispatch in reduce_kernels.hip)
 // ---------------------------------------------------------------------------
-// srcs: host array of k device pointers. k == 1 copies.
-// round_each: bf16 and fp16 sums round to their format after every add (no effect
-// on other dtypes or ops).
-// shape: bottom-up widths of a nested fold (srcs in depth-first leaf order,
-// product == k, at most kMaxFoldLevels levels; bf16 and fp16 inner nodes rounded);
-// nlevels <= 1 = flat.  Only float sums depend on it: integer sums, AND, MAX and
-// MIN are associative and take the flat kernel.
-// scale (SUM of f32, f64, bf16, fp16, fp8 only; else FTAR_ERR_UNSUPPORTED): the fold finishes as
-// round_to_dtype(A * r), A its accumulator before the one rounding (fp32 for the 16- and 8-bit floats; a nested
-// fold's root, inner nodes rounded as ever), r = *scale cast to float (f64: as it is); round_each folds
-// then round before each add, so the last sum reaches the multiply unrounded; k == 1 is a scaled copy.
-// op = FTAR_AVG is refused here: the engine runs it as SUM with a scale on root items (root_scale).
-// amax (only with a scale; f32, bf16, fp16, fp8, else FTAR_ERR_UNSUPPORTED): the launch also maxes the fp32
-// bits of the largest |stored value| into *amax (device memory), one no-return atomicMax per workgroup; the
-// caller zeroes the word before the first launch, and every piece of one fold passes the same word.
 constexpr int kMaxFoldLevels = 4;
-ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                            hipStream_t stream, bool round_each = false, const int* shape = nullptr,
-                            int nlevels = 0, bool lds = true, const double* scale = nullptr,
-                            unsigned* amax = nullptr);
+// One fold: dst[i] = srcs[0][i] OP ... OP srcs[k-1][i] on `count` elements of dtype dt.  Callers set the fields by
+// name; what they leave out is a plain flat SUM on the null stream.
+struct FoldCall {
+  const void* const* srcs = nullptr;  // host array of k device pointers
+  int k = 0;                          // 1 .. FTAR_MAX_K; k == 1 copies
+  void* dst = nullptr;                // may be one of the sources
+  size_t count = 0;
+  ftar_dtype_t dt = FTAR_UINT8;
+  // FTAR_AVG is refused: the engine runs it as SUM with a scale on root items (FoldOp::scale)
+  ftar_op_t op = FTAR_SUM;
+  hipStream_t stream = nullptr;
+  // bf16, fp16 and fp8 sums round to their format after every add (no effect on other dtypes or ops)
+  bool round_each = false;
+  // bottom-up widths of a nested fold (srcs in depth-first leaf order, product == k, at most kMaxFoldLevels
+  // levels; bf16, fp16 and fp8 inner nodes rounded); nlevels <= 1 = flat.  Only float sums depend on it: integer
+  // sums, AND, MAX and MIN are associative and take the flat kernel.
+  const int* shape = nullptr;
+  int nlevels = 0;
+  // false: the register kernels from k = 3 on and for nested folds (the peer forms' ":vec" dispatch, the A/B
+  // reference of the LDS-staged kernels)
+  bool lds = true;
+  // SUM of f32, f64, bf16, fp16, fp8 only, else FTAR_ERR_UNSUPPORTED: the fold finishes as
+  // round_to_dtype(A * r), A its accumulator before the one rounding (fp32 for the 16- and 8-bit floats; a nested
+  // fold's root, inner nodes rounded as ever), r = *scale cast to float (f64: as it is); round_each folds then
+  // round before each add, so the last sum reaches the multiply unrounded; k == 1 is a scaled copy.
+  const double* scale = nullptr;
+  // only with a scale; f32, bf16, fp16, fp8, else FTAR_ERR_UNSUPPORTED: the launch also maxes the fp32 bits of
+  // the largest |stored value| into *amax (device memory), one no-return atomicMax per workgroup; the caller
+  // zeroes the word before the first launch, and every piece of one fold passes the same word.
+  unsigned* amax = nullptr;
+};
+ftar_status_t launch_reduce(const FoldCall& f);
 bool dtype_op_supported(ftar_dtype_t dt, ftar_op_t op);  // the AllReduce entry points' matrix (AVG included)
 bool dtype_scalable(ftar_dtype_t dt);                    // the six float dtypes
 bool dtype_has_amax(ftar_dtype_t dt);                    // ... whose amax fits a float: all but f64
@@ -186,15 +199,11 @@ ftar_status_t amax_supported(ftar_dtype_t dt, ftar_op_t op);
 // levels on every width >= 1 with the product k; else FTAR_ERR_INVALID_ARG
 ftar_status_t check_fold_shape(const int* shape, int nlevels, int k);
 // launch_reduce's amax finish of f32, bf16 and fp16 (reduce_amax.hip, a translation unit of its own as
-// reduce_f8.hip is; fp8's amax finish is in that one); arguments already checked, k >= 1, count > 0
-ftar_status_t launch_reduce_amax(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt,
-                                 hipStream_t stream, bool round_each, const int* shape, int nlevels, bool lds,
-                                 double scale, unsigned* amax);
+// reduce_f8.hip is; fp8's amax finish is in that one); the call already checked: k >= 1, count > 0, scale and amax set
+ftar_status_t launch_reduce_amax(const FoldCall& f);
 // launch_reduce's fp8 half (reduce_f8.hip, a translation unit of its own: it compiles beside
-// reduce_kernels.hip); arguments already checked, k >= 1, count > 0, op one of SUM, MAX, MIN
-ftar_status_t launch_reduce_f8(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                               hipStream_t stream, bool round_each, const int* shape, int nlevels, bool lds,
-                               const double* scale, unsigned* amax = nullptr);
+// reduce_kernels.hip); the call already checked: k >= 1, count > 0, op one of SUM, MAX, MIN
+ftar_status_t launch_reduce_f8(const FoldCall& f);
 // AVG on the engine's folds: the op the kernels run (SUM) and the scale of item r (1 / P as a float, f64:
 // as a double, on root items; none elsewhere).  Other ops pass through.
 // amax (an amax call, ftar_allreduce_amax; SUM or AVG): root items also max into that word, SUM's with the

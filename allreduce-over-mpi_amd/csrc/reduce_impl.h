@@ -69,7 +69,7 @@ inline thread_local const void* g_last_kernel = nullptr;
 
 namespace {
 
-constexpr int kFinPlain = 0, kFinScaled = 1, kFinAmax = 2;  // FTAR_LAUNCH_FIN's SC (false / true: the first two)
+constexpr int kFinPlain = 0, kFinScaled = 1, kFinAmax = 2;  // FTAR_LAUNCH_FIN's SC
 constexpr int kThreads = 256;
 constexpr int kTreeLevels = kMaxFoldLevels;
 // Measured on MI355X with COLD data (tools/kbench_cold.py: launches rotate over
@@ -976,21 +976,6 @@ __global__ void __launch_bounds__(W * 64)
   reduce_lds_body<Tr, K, U, W, AUX, PROG>(src, dst, nvec, head, tail, AmaxFin<Tr>{scale, amax});
 }
 
-template <class Tr, int K, int U, int W = 4, int AUX = 2, bool PROG = true, int SC = kFinPlain>
-hipError_t launch_lds(const void* const* srcs, void* dst, size_t nvec, hipStream_t s, int head = 0, int tail = 0,
-                      double r = 1.0, unsigned* am = nullptr) {
-  if constexpr (W * U * K > 160) {
-    return hipErrorInvalidValue;
-  } else {
-    const size_t per_block = (size_t)W * U * 64;
-    const size_t blocks = (nvec + per_block - 1) / per_block;
-    const dim3 grid((unsigned)(blocks ? blocks : 1));
-    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_lds, (Tr, K, U, W, AUX, PROG), grid, dim3(W * 64), 0, s,
-                    pack_srcs<K>(srcs, K), dst, nvec, head, tail);
-    return hipGetLastError();
-  }
-}
-
 // element-wise fallback for sources not co-aligned with dst
 template <class Tr, class Fin>
 __device__ __forceinline__ void reduce_elem_body(const Srcs<FTAR_MAX_K>& src, int k, void* dst, size_t n, Fin fin) {
@@ -1399,6 +1384,21 @@ __global__ void __launch_bounds__(kThreads) gather_logged_kernel(SegArgs a, int 
 // host-side launch
 // ---------------------------------------------------------------------------
 
+// What every launcher below takes of one fold, beside the geometry it launches on: the k sources, the
+// destination, the stream, and the two arguments of the finishes (r: the scale of the scaled and the amax finish;
+// am: the amax word of the latter; a plain launch reads neither).
+struct Launch {
+  const void* const* srcs;
+  int k;
+  void* dst;
+  hipStream_t s;
+  double r = 1.0;
+  unsigned* am = nullptr;
+};
+inline Launch launch_of(const FoldCall& f) {
+  return {f.srcs, f.k, f.dst, f.stream, f.scale ? *f.scale : 1.0, f.amax};
+}
+
 // How `count` elements of `esz` bytes at dst split for 16-byte access (launch_tr, launch_tree, launch_copy):
 // `head` elements up to dst's first aligned address, nvec vectors, `tail` elements (head and tail are workgroup
 // 0's, element-wise, in the same launch).  co_aligned: dst is element-aligned and every source sits at dst's
@@ -1421,32 +1421,42 @@ inline Split16 split16(const void* const* srcs, int k, const void* dst, size_t c
 // grid of the element-wise kernels: grid-stride beyond 8192 workgroups
 inline unsigned elem_blocks(size_t count) { return (unsigned)std::min<size_t>((count + kThreads - 1) / kThreads, 8192); }
 
+template <class Tr, int K, int U, int W = 4, int AUX = 2, bool PROG = true, int SC = kFinPlain>
+hipError_t launch_lds(const Launch& c, const Split16& sp) {
+  if constexpr (W * U * K > 160) {
+    return hipErrorInvalidValue;
+  } else {
+    const size_t per_block = (size_t)W * U * 64;
+    const size_t blocks = (sp.nvec + per_block - 1) / per_block;
+    const dim3 grid((unsigned)(blocks ? blocks : 1));
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)c.r, c.am, reduce_lds, (Tr, K, U, W, AUX, PROG), grid, dim3(W * 64), 0, c.s,
+                    pack_srcs<K>(c.srcs, K), c.dst, sp.nvec, sp.head, sp.tail);
+    return hipGetLastError();
+  }
+}
+
 template <class Tr, int K, int U, bool NTL, bool NTS, int BS, int SC = kFinPlain>
-hipError_t launch_cfg(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
-                      size_t max_blocks, double r = 1.0, unsigned* am = nullptr) {
+hipError_t launch_cfg(const Launch& c, const Split16& sp, size_t max_blocks = 0) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
   const size_t per_block = (size_t)U * BS;
-  size_t blocks = (nvec + per_block - 1) / per_block;
+  size_t blocks = (sp.nvec + per_block - 1) / per_block;
   if (blocks == 0) blocks = 1;  // head/tail only
   if (max_blocks && blocks > max_blocks) blocks = max_blocks;  // grid-stride over the rest
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_vec, (Tr, K, U, NTL, NTS, BS), dim3((unsigned)blocks), dim3(BS), 0, s,
-                  pack_srcs<KK>(srcs, k), k, dst, nvec, head, tail);
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)c.r, c.am, reduce_vec, (Tr, K, U, NTL, NTS, BS), dim3((unsigned)blocks), dim3(BS), 0,
+                  c.s, pack_srcs<KK>(c.srcs, c.k), c.k, c.dst, sp.nvec, sp.head, sp.tail);
   return hipGetLastError();
 }
 
 template <class Tr, int K, int SC = kFinPlain>
-hipError_t launch_k(const void* const* srcs, int k, void* dst, size_t nvec, int head, int tail, hipStream_t s,
-                    double r = 1.0, unsigned* am = nullptr) {
+hipError_t launch_k(const Launch& c, const Split16& sp) {
   // the amax finish ends every workgroup with a reduction and one L2 read: the 4-byte k = 2 shape of two-wave,
   // one-tile workgroups (131,072 of them on 256 MiB) pays it eight times as often as 4 x 4, the 2-byte shape
   constexpr bool kWide = SC == kFinAmax && K == 2 && sizeof(typename Tr::S) >= 4;
   if constexpr (K >= 2)
-    return launch_lds<Tr, K, (kWide ? 4 : kLdsTiles<Tr, K>), (kWide ? 4 : kLdsWaves<Tr, K>), 2, true, SC>(
-        srcs, dst, nvec, s, head, tail, r, am);
+    return launch_lds<Tr, K, (kWide ? 4 : kLdsTiles<Tr, K>), (kWide ? 4 : kLdsWaves<Tr, K>), 2, true, SC>(c, sp);
   else
-    return launch_cfg<Tr, K, kUnroll, kNtLoads, kNtStores, kVecThreads, SC>(srcs, k, dst, nvec, head, tail, s, 0, r,
-                                                                            am);
+    return launch_cfg<Tr, K, kUnroll, kNtLoads, kNtStores, kVecThreads, SC>(c, sp);
 }
 
 // Leaf codes of a nested fold with bottom-up widths shape[0..nlevels) over k
@@ -1462,44 +1472,46 @@ bool make_tree_code(const int* shape, int nlevels, int k, TreeCode* tc) {
   for (int j = 0; j < k; ++j) tc->c[j] = (unsigned char)leaf_code(shape, nlevels, j);
   return true;
 }
+// A nested fold on the host: its widths (launch_tree picks the compile-time shapes by them) and the leaf codes
+// make_tree_code made of them (the kernels' argument).
+struct Tree {
+  const int* shape;
+  int nlevels;
+  TreeCode code;
+};
 
 template <class Tr, int K, int U, class Sh = RuntimeShape, int SC = kFinPlain>
-hipError_t launch_tree_k(const void* const* srcs, int k, const TreeCode& tc, void* dst, size_t nvec, int head,
-                         int tail, hipStream_t s, double r = 1.0, unsigned* am = nullptr) {
+hipError_t launch_tree_k(const Launch& c, const Tree& t, const Split16& sp) {
   constexpr int KK = K > 0 ? K : FTAR_MAX_K;
-  size_t blocks = (nvec + (size_t)U * kThreads - 1) / ((size_t)U * kThreads);
+  size_t blocks = (sp.nvec + (size_t)U * kThreads - 1) / ((size_t)U * kThreads);
   if (blocks == 0) blocks = 1;
   if (blocks > 0x7fffffffull) blocks = 0x7fffffffull;
-  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_tree, (Tr, K, U, Sh), dim3((unsigned)blocks), dim3(kThreads), 0, s,
-                  pack_srcs<KK>(srcs, k), k, tc, dst, nvec, head, tail);
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)c.r, c.am, reduce_tree, (Tr, K, U, Sh), dim3((unsigned)blocks), dim3(kThreads), 0,
+                  c.s, pack_srcs<KK>(c.srcs, c.k), c.k, t.code, c.dst, sp.nvec, sp.head, sp.tail);
   return hipGetLastError();
 }
 
 template <class Tr, int K, class Sh = RuntimeShape, int SC = kFinPlain>
-hipError_t launch_tree_lds(const void* const* srcs, const TreeCode& tc, void* dst, size_t nvec, int head, int tail,
-                           hipStream_t s, double r = 1.0, unsigned* am = nullptr) {
+hipError_t launch_tree_lds(const Launch& c, const Tree& t, const Split16& sp) {
   constexpr int U = kLdsTiles<Tr, K>, W = kLdsWaves<Tr, K>;
   const size_t per_block = (size_t)W * U * 64;
-  const size_t blocks = (nvec + per_block - 1) / per_block;
-  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_tree_lds, (Tr, K, U, W, Sh), dim3((unsigned)(blocks ? blocks : 1)),
-                  dim3(W * 64), 0, s, pack_srcs<K>(srcs, K), tc, dst, nvec, head, tail);
+  const size_t blocks = (sp.nvec + per_block - 1) / per_block;
+  FTAR_LAUNCH_FIN(SC, (typename Tr::SC)c.r, c.am, reduce_tree_lds, (Tr, K, U, W, Sh), dim3((unsigned)(blocks ? blocks : 1)),
+                  dim3(W * 64), 0, c.s, pack_srcs<K>(c.srcs, K), t.code, c.dst, sp.nvec, sp.head, sp.tail);
   return hipGetLastError();
 }
 
 template <class Tr, int SC = kFinPlain>
-hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const int* shape, int nlevels, void* dst,
-                       size_t count, hipStream_t s, bool lds, double r = 1.0, unsigned* am = nullptr) {
+hipError_t launch_tree(const Launch& c, const Tree& t, size_t count, bool lds) {
   using S = typename Tr::S;
-  const Split16 sp = split16(srcs, k, dst, count, sizeof(S));
+  const Split16 sp = split16(c.srcs, c.k, c.dst, count, sizeof(S));
   if (!sp.co_aligned) {
-    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_tree_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
-                    pack_srcs<FTAR_MAX_K>(srcs, k), k, tc, dst, count);
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)c.r, c.am, reduce_tree_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0,
+                    c.s, pack_srcs<FTAR_MAX_K>(c.srcs, c.k), c.k, t.code, c.dst, count);
     return hipGetLastError();
   }
-  const size_t nvec = sp.nvec;
-  const int h = sp.head, tail = sp.tail;
   auto is = [&](std::initializer_list<int> w) {
-    return (int)w.size() == nlevels && std::equal(w.begin(), w.end(), shape);
+    return (int)w.size() == t.nlevels && std::equal(w.begin(), w.end(), t.shape);
   };
   // the multi-stage trees of 4, 8 and 16 ranks: compile-time shapes.
   // LDS-staged (production, round 2): cold A/B against the register kernel
@@ -1508,67 +1520,88 @@ hipError_t launch_tree(const void* const* srcs, int k, const TreeCode& tc, const
   // v_cvt_pk_bf16_f32 (kLdsDeepBf16) on (2,2,2) and (2,2,2,2) too; its
   // runtime-coded folds still lose there and keep the register kernel.
   if (lds) {
-    if (is({2, 2})) return launch_tree_lds<Tr, 4, StaticShape<2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-    if (is({2, 4})) return launch_tree_lds<Tr, 8, StaticShape<2, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-    if (is({4, 2})) return launch_tree_lds<Tr, 8, StaticShape<4, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-    if (is({4, 4})) return launch_tree_lds<Tr, 16, StaticShape<4, 4>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    if (is({2, 2})) return launch_tree_lds<Tr, 4, StaticShape<2, 2>, SC>(c, t, sp);
+    if (is({2, 4})) return launch_tree_lds<Tr, 8, StaticShape<2, 4>, SC>(c, t, sp);
+    if (is({4, 2})) return launch_tree_lds<Tr, 8, StaticShape<4, 2>, SC>(c, t, sp);
+    if (is({4, 4})) return launch_tree_lds<Tr, 16, StaticShape<4, 4>, SC>(c, t, sp);
   }
   if (lds && (sizeof(S) >= 4 || kLdsDeepBf16)) {
-    if (is({2, 2, 2})) return launch_tree_lds<Tr, 8, StaticShape<2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-    if (is({2, 2, 2, 2})) return launch_tree_lds<Tr, 16, StaticShape<2, 2, 2, 2>, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    if (is({2, 2, 2})) return launch_tree_lds<Tr, 8, StaticShape<2, 2, 2>, SC>(c, t, sp);
+    if (is({2, 2, 2, 2})) return launch_tree_lds<Tr, 16, StaticShape<2, 2, 2, 2>, SC>(c, t, sp);
   }
   if (lds && sizeof(S) >= 4) {
-    switch (k) {  // other shapes: runtime leaf codes
-      case 4: return launch_tree_lds<Tr, 4, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-      case 6: return launch_tree_lds<Tr, 6, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-      case 8: return launch_tree_lds<Tr, 8, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-      case 9: return launch_tree_lds<Tr, 9, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-      case 12: return launch_tree_lds<Tr, 12, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
-      case 16: return launch_tree_lds<Tr, 16, RuntimeShape, SC>(srcs, tc, dst, nvec, h, tail, s, r, am);
+    switch (c.k) {  // other shapes: runtime leaf codes
+      case 4: return launch_tree_lds<Tr, 4, RuntimeShape, SC>(c, t, sp);
+      case 6: return launch_tree_lds<Tr, 6, RuntimeShape, SC>(c, t, sp);
+      case 8: return launch_tree_lds<Tr, 8, RuntimeShape, SC>(c, t, sp);
+      case 9: return launch_tree_lds<Tr, 9, RuntimeShape, SC>(c, t, sp);
+      case 12: return launch_tree_lds<Tr, 12, RuntimeShape, SC>(c, t, sp);
+      case 16: return launch_tree_lds<Tr, 16, RuntimeShape, SC>(c, t, sp);
       default: break;
     }
-    return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+    return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(c, t, sp);
   }
   // registers (round 1; the A/B reference of ftar_debug_reduce_nested_lds)
-  if (is({2, 2})) return launch_tree_k<Tr, 4, 2, StaticShape<2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-  if (is({2, 4})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-  if (is({4, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<4, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-  if (is({2, 2, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-  if (is({4, 4})) return launch_tree_k<Tr, 16, 1, StaticShape<4, 4>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-  if (is({2, 2, 2, 2})) return launch_tree_k<Tr, 16, 1, StaticShape<2, 2, 2, 2>, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-  switch (k) {  // other shapes: runtime leaf codes; 16 sources fit one vector per lane
-    case 4: return launch_tree_k<Tr, 4, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-    case 6: return launch_tree_k<Tr, 6, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-    case 8: return launch_tree_k<Tr, 8, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-    case 16: return launch_tree_k<Tr, 16, 1, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
-    default: return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(srcs, k, tc, dst, nvec, h, tail, s, r, am);
+  if (is({2, 2})) return launch_tree_k<Tr, 4, 2, StaticShape<2, 2>, SC>(c, t, sp);
+  if (is({2, 4})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 4>, SC>(c, t, sp);
+  if (is({4, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<4, 2>, SC>(c, t, sp);
+  if (is({2, 2, 2})) return launch_tree_k<Tr, 8, 2, StaticShape<2, 2, 2>, SC>(c, t, sp);
+  if (is({4, 4})) return launch_tree_k<Tr, 16, 1, StaticShape<4, 4>, SC>(c, t, sp);
+  if (is({2, 2, 2, 2})) return launch_tree_k<Tr, 16, 1, StaticShape<2, 2, 2, 2>, SC>(c, t, sp);
+  switch (c.k) {  // other shapes: runtime leaf codes; 16 sources fit one vector per lane
+    case 4: return launch_tree_k<Tr, 4, 2, RuntimeShape, SC>(c, t, sp);
+    case 6: return launch_tree_k<Tr, 6, 2, RuntimeShape, SC>(c, t, sp);
+    case 8: return launch_tree_k<Tr, 8, 2, RuntimeShape, SC>(c, t, sp);
+    case 16: return launch_tree_k<Tr, 16, 1, RuntimeShape, SC>(c, t, sp);
+    default: return launch_tree_k<Tr, 0, 2, RuntimeShape, SC>(c, t, sp);
   }
 }
 
-// HOT: the largest k with an unrolled LDS-staged kernel (fp32/bf16/fp16 16, the other types, fp8 included, 8; 0 = k = 2
-// only); larger k take the runtime-k register kernel.  The other types gained 4-6 % at k = 8 on the
-// LDS kernel (tools/dtype_rates.py, profiles/r02/s4/dtype_rates*.log).
+// The flat fold.  HOT: the largest k with an unrolled LDS-staged kernel (fp32/bf16/fp16 16, the other types, fp8
+// included, 8); larger k take the runtime-k register kernel, and so does every k > 2 when lds is false (the peer
+// forms' ":vec" A/B).  The other types gained 4-6 % at k = 8 on the LDS kernel (tools/dtype_rates.py,
+// profiles/r02/s4/dtype_rates*.log).
 template <class Tr, int HOT, int SC = kFinPlain>
-hipError_t launch_tr(const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0,
-                     unsigned* am = nullptr) {
-  const Split16 sp = split16(srcs, k, dst, count, sizeof(typename Tr::S));
+hipError_t launch_tr(const Launch& c, size_t count, bool lds = true) {
+  static_assert(HOT >= 2);
+  const Split16 sp = split16(c.srcs, c.k, c.dst, count, sizeof(typename Tr::S));
   if (!sp.co_aligned) {
-    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)r, am, reduce_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, s,
-                    pack_srcs<FTAR_MAX_K>(srcs, k), k, dst, count);
+    FTAR_LAUNCH_FIN(SC, (typename Tr::SC)c.r, c.am, reduce_elem, (Tr), dim3(elem_blocks(count)), dim3(kThreads), 0, c.s,
+                    pack_srcs<FTAR_MAX_K>(c.srcs, c.k), c.k, c.dst, count);
     return hipGetLastError();
   }
   hipError_t e = hipErrorInvalidValue;
   bool done = false;
-  [&]<int... I>(std::integer_sequence<int, I...>) {  // k = 2 .. max(2, HOT), unrolled
-    ((k == I + 2 && (I + 2 == 2 || I + 2 <= HOT)
-          ? (e = launch_k<Tr, (I + 2 <= (HOT > 2 ? HOT : 2) ? I + 2 : 2), SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail,
-                                                                              s, r, am),
-             done = true)
-          : false),
-     ...);
-  }(std::make_integer_sequence<int, (HOT > 2 ? HOT : 2) - 1>{});
+  [&]<int... I>(std::integer_sequence<int, I...>) {  // k = 2 .. HOT, unrolled
+    ((c.k == I + 2 && (I + 2 == 2 || lds) ? (e = launch_k<Tr, I + 2, SC>(c, sp), done = true) : false), ...);
+  }(std::make_integer_sequence<int, HOT - 1>{});
   if (done) return e;
-  return launch_k<Tr, 0, SC>(srcs, k, dst, sp.nvec, sp.head, sp.tail, s, r, am);
+  return launch_k<Tr, 0, SC>(c, sp);
+}
+
+// One dtype's SUM in the finish SC, nested or flat -- the one place that decides between the nested kernels, a
+// one-round ring hop and the flat fold.  Sum: the dtype's trait; Hop: the one of a one-round ring fold
+// (round_each, k > 2), which rounds to the format after every add; HopPre: its form under a scaled or an amax
+// finish, which rounds before each add instead, so the last sum reaches the finish unrounded, as the staged
+// ring's last hop (a plain k = 2 fold) hands it over.  f32 and f64, which round nowhere, pass Sum for both.  Only
+// the hop trait of this finish is named, so only its kernels are instantiated: a plain launch never names a
+// HopPre kernel, nor a scaled or amax one a Hop kernel.  TREE_LDS false (f64): nested folds stay on the register
+// kernels.
+template <class Sum, class Hop, class HopPre, int HOT, int SC, bool TREE_LDS = true>
+ftar_status_t launch_sum(const FoldCall& f) {
+  const Launch c = launch_of(f);
+  hipError_t e;
+  if (f.nlevels > 1 && f.k > 1) {
+    Tree t{f.shape, f.nlevels, {}};
+    if (!f.shape || !make_tree_code(f.shape, f.nlevels, f.k, &t.code)) return FTAR_ERR_INVALID_ARG;
+    e = launch_tree<Sum, SC>(c, t, f.count, f.lds && TREE_LDS);
+  } else if (f.round_each && f.k > 2) {
+    e = launch_tr<std::conditional_t<SC != kFinPlain, HopPre, Hop>, HOT, SC>(c, f.count, f.lds);
+  } else {
+    e = launch_tr<Sum, HOT, SC>(c, f.count, f.lds);
+  }
+  FTAR_CHECK_HIP(e);
+  return FTAR_SUCCESS;
 }
 
 }  // namespace

@@ -117,65 +117,35 @@ ftar_status_t launch_noop(hipStream_t stream) {
 }
 
 namespace {
-// the LDS-staged kernel up to k = HOT, or (lds == false: the peer forms' ":vec" A/B) only at k = 2
-template <class Tr, int HOT, bool SC = false>
-hipError_t tr(bool lds, const void* const* srcs, int k, void* dst, size_t count, hipStream_t s, double r = 1.0) {
-  return lds ? launch_tr<Tr, HOT, SC>(srcs, k, dst, count, s, r) : launch_tr<Tr, 0, SC>(srcs, k, dst, count, s, r);
-}
 // MAX / MIN of one dtype; HOT as the SUM of the same element width
 template <bool MAX>
-hipError_t tr_min_max(ftar_dtype_t dt, bool lds, const void* const* srcs, int k, void* dst, size_t count,
-                      hipStream_t s) {
-  switch (dt) {
-    case FTAR_UINT8: return tr<MinMax<unsigned char, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_INT8: return tr<MinMax<signed char, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_UINT16: return tr<MinMax<unsigned short, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_INT16: return tr<MinMax<short, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_INT32: return tr<MinMax<int, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_INT64: return tr<MinMax<long long, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_FLOAT32: return tr<MinMax<float, MAX>, 16>(lds, srcs, k, dst, count, s);
-    case FTAR_FLOAT64: return tr<MinMax<double, MAX>, 8>(lds, srcs, k, dst, count, s);
-    case FTAR_BFLOAT16: return tr<BF16MinMax<MAX>, 16>(lds, srcs, k, dst, count, s);
-    case FTAR_FLOAT16: return tr<MinMax<_Float16, MAX>, 16>(lds, srcs, k, dst, count, s);
+hipError_t min_max(const FoldCall& f) {
+  const Launch c = launch_of(f);
+  switch (f.dt) {
+    case FTAR_UINT8: return launch_tr<MinMax<unsigned char, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_INT8: return launch_tr<MinMax<signed char, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_UINT16: return launch_tr<MinMax<unsigned short, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_INT16: return launch_tr<MinMax<short, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_INT32: return launch_tr<MinMax<int, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_INT64: return launch_tr<MinMax<long long, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_FLOAT32: return launch_tr<MinMax<float, MAX>, 16>(c, f.count, f.lds);
+    case FTAR_FLOAT64: return launch_tr<MinMax<double, MAX>, 8>(c, f.count, f.lds);
+    case FTAR_BFLOAT16: return launch_tr<BF16MinMax<MAX>, 16>(c, f.count, f.lds);
+    case FTAR_FLOAT16: return launch_tr<MinMax<_Float16, MAX>, 16>(c, f.count, f.lds);
     case FTAR_FLOAT8_E4M3: case FTAR_FLOAT8_E5M2: break;  // launch_reduce_f8
     case FTAR_BOOL: break;
   }
   return hipErrorInvalidValue;
 }
-// The float sums, nested or flat, in either finish: SC = the scaled finish (AVG's root folds,
-// ftar_reduce_scaled) with the scale r.  A one-round ring fold (round_each, k > 2) of a 16-bit format rounds
-// after every add; under a scaled finish it rounds before each add instead (H16SumHopPreT), so the last sum
-// reaches the finish unrounded, as the staged ring's last hop (a plain k = 2 fold) hands it over.
-template <bool SC>
-ftar_status_t float_sum(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, hipStream_t s,
-                        bool round_each, const int* shape, int nlevels, bool lds, double r) {
-  hipError_t e = hipErrorInvalidValue;
-  const bool hop = round_each && k > 2;
-  if (nlevels > 1 && k > 1) {
-    TreeCode tc;
-    if (!shape || !make_tree_code(shape, nlevels, k, &tc)) return FTAR_ERR_INVALID_ARG;
-    switch (dt) {
-      case FTAR_FLOAT32: e = launch_tree<F32Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
-      case FTAR_FLOAT64: e = launch_tree<F64Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, false, r); break;
-      case FTAR_FLOAT16: e = launch_tree<F16Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
-      default: e = launch_tree<BF16Sum, SC>(srcs, k, tc, shape, nlevels, dst, count, s, lds, r); break;
-    }
-  } else {
-    switch (dt) {
-      case FTAR_FLOAT32: e = tr<F32Sum, 16, SC>(lds, srcs, k, dst, count, s, r); break;
-      case FTAR_FLOAT64: e = tr<F64Sum, 8, SC>(lds, srcs, k, dst, count, s, r); break;
-      case FTAR_FLOAT16:
-        e = hop ? tr<std::conditional_t<SC, F16SumHopPre, F16SumHop>, 16, SC>(lds, srcs, k, dst, count, s, r)
-                : tr<F16Sum, 16, SC>(lds, srcs, k, dst, count, s, r);
-        break;
-      default:
-        e = hop ? tr<std::conditional_t<SC, BF16SumHopPre, BF16SumHop>, 16, SC>(lds, srcs, k, dst, count, s, r)
-                : tr<BF16Sum, 16, SC>(lds, srcs, k, dst, count, s, r);
-        break;
-    }
+// The float sums (fp8's: reduce_f8.hip) in the plain or the scaled finish (AVG's root folds, ftar_reduce_scaled)
+template <int SC>
+ftar_status_t float_sum(const FoldCall& f) {
+  switch (f.dt) {
+    case FTAR_FLOAT32: return launch_sum<F32Sum, F32Sum, F32Sum, 16, SC>(f);
+    case FTAR_FLOAT64: return launch_sum<F64Sum, F64Sum, F64Sum, 8, SC, false>(f);
+    case FTAR_FLOAT16: return launch_sum<F16Sum, F16SumHop, F16SumHopPre, 16, SC>(f);
+    default: return launch_sum<BF16Sum, BF16SumHop, BF16SumHopPre, 16, SC>(f);
   }
-  FTAR_CHECK_HIP(e);
-  return FTAR_SUCCESS;
 }
 }  // namespace
 
@@ -191,54 +161,50 @@ ftar_status_t launch_copy(const void* src, void* dst, size_t bytes, hipStream_t 
     const Segment seg{src, dst, bytes};
     return launch_gather(&seg, 1, s);
   }
-  FTAR_CHECK_HIP((launch_lds<U8Sum, 1, 1, 1>(srcs, dst, sp.nvec, s, sp.head, sp.tail)));
+  FTAR_CHECK_HIP((launch_lds<U8Sum, 1, 1, 1>(Launch{srcs, 1, dst, s}, sp)));
   return FTAR_SUCCESS;
 }
 
-ftar_status_t launch_reduce(const void* const* srcs, int k, void* dst, size_t count, ftar_dtype_t dt, ftar_op_t op,
-                            hipStream_t s, bool round_each, const int* shape, int nlevels, bool lds,
-                            const double* scale, unsigned* amax) {
-  if (k < 1 || k > FTAR_MAX_K || !srcs || !dst) return FTAR_ERR_INVALID_ARG;
-  if (op == FTAR_AVG || !dtype_op_supported(dt, op)) return FTAR_ERR_UNSUPPORTED;  // AVG: the engine's SUM + scale
-  if (scale && (op != FTAR_SUM || !dtype_scalable(dt))) return FTAR_ERR_UNSUPPORTED;
-  if (amax && (!scale || !dtype_has_amax(dt))) return FTAR_ERR_UNSUPPORTED;
-  if (count == 0) return FTAR_SUCCESS;
-  for (int j = 0; j < k; ++j)
-    if (!srcs[j]) return FTAR_ERR_INVALID_ARG;
-  if (dt == FTAR_FLOAT8_E4M3 || dt == FTAR_FLOAT8_E5M2)  // every fp8 fold: reduce_f8.hip
-    return launch_reduce_f8(srcs, k, dst, count, dt, op, s, round_each, shape, nlevels, lds, scale, amax);
-  if (amax)  // the amax finish of f32, bf16 and fp16: reduce_amax.hip
-    return launch_reduce_amax(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale, amax);
+ftar_status_t launch_reduce(const FoldCall& f) {
+  if (f.k < 1 || f.k > FTAR_MAX_K || !f.srcs || !f.dst) return FTAR_ERR_INVALID_ARG;
+  if (f.op == FTAR_AVG || !dtype_op_supported(f.dt, f.op)) return FTAR_ERR_UNSUPPORTED;  // AVG: the engine's SUM + scale
+  if (f.scale && (f.op != FTAR_SUM || !dtype_scalable(f.dt))) return FTAR_ERR_UNSUPPORTED;
+  if (f.amax && (!f.scale || !dtype_has_amax(f.dt))) return FTAR_ERR_UNSUPPORTED;
+  if (f.count == 0) return FTAR_SUCCESS;
+  for (int j = 0; j < f.k; ++j)
+    if (!f.srcs[j]) return FTAR_ERR_INVALID_ARG;
+  if (f.dt == FTAR_FLOAT8_E4M3 || f.dt == FTAR_FLOAT8_E5M2) return launch_reduce_f8(f);  // every fp8 fold: reduce_f8.hip
+  if (f.amax) return launch_reduce_amax(f);  // the amax finish of f32, bf16 and fp16: reduce_amax.hip
   // a scaled k = 1 is a scaled copy through the runtime-k kernel; a plain one is a copy
-  if (scale) return float_sum<true>(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, *scale);
-  if (k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)
-    return launch_copy(srcs[0], dst, count * dtype_size(dt), s);
-  if (op == FTAR_SUM && dtype_scalable(dt))
-    return float_sum<false>(srcs, k, dst, count, dt, s, round_each, shape, nlevels, lds, 1.0);
+  if (f.scale) return float_sum<kFinScaled>(f);
+  if (f.k == 1)  // vector_add/reduce_sum.h:36-47: a copy (a streaming kernel, not the DMA blit)
+    return launch_copy(f.srcs[0], f.dst, f.count * dtype_size(f.dt), f.stream);
+  if (f.op == FTAR_SUM && dtype_scalable(f.dt)) return float_sum<kFinPlain>(f);
+  const Launch c = launch_of(f);
   hipError_t e = hipErrorInvalidValue;
-  switch (op) {
+  switch (f.op) {
   case FTAR_SUM:
-    switch (dt) {
+    switch (f.dt) {
       case FTAR_FLOAT32: case FTAR_FLOAT64: case FTAR_BFLOAT16: case FTAR_FLOAT16: break;  // float_sum above
       case FTAR_FLOAT8_E4M3: case FTAR_FLOAT8_E5M2: break;  // launch_reduce_f8 above
-      case FTAR_UINT8: case FTAR_INT8: e = tr<U8Sum, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_UINT16: case FTAR_INT16: e = tr<U16Sum, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_INT32: e = tr<U32Sum, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_INT64: e = tr<U64Sum, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_BOOL: e = tr<BoolSum, 8>(lds, srcs, k, dst, count, s); break;
+      case FTAR_UINT8: case FTAR_INT8: e = launch_tr<U8Sum, 8>(c, f.count, f.lds); break;
+      case FTAR_UINT16: case FTAR_INT16: e = launch_tr<U16Sum, 8>(c, f.count, f.lds); break;
+      case FTAR_INT32: e = launch_tr<U32Sum, 8>(c, f.count, f.lds); break;
+      case FTAR_INT64: e = launch_tr<U64Sum, 8>(c, f.count, f.lds); break;
+      case FTAR_BOOL: e = launch_tr<BoolSum, 8>(c, f.count, f.lds); break;
     }
     break;
   case FTAR_BAND:
-    switch (dt) {
-      case FTAR_UINT8: case FTAR_INT8: e = tr<Band<unsigned char>, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_UINT16: case FTAR_INT16: e = tr<Band<unsigned short>, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_INT32: e = tr<Band<unsigned>, 8>(lds, srcs, k, dst, count, s); break;
-      case FTAR_INT64: e = tr<Band<unsigned long long>, 8>(lds, srcs, k, dst, count, s); break;
+    switch (f.dt) {
+      case FTAR_UINT8: case FTAR_INT8: e = launch_tr<Band<unsigned char>, 8>(c, f.count, f.lds); break;
+      case FTAR_UINT16: case FTAR_INT16: e = launch_tr<Band<unsigned short>, 8>(c, f.count, f.lds); break;
+      case FTAR_INT32: e = launch_tr<Band<unsigned>, 8>(c, f.count, f.lds); break;
+      case FTAR_INT64: e = launch_tr<Band<unsigned long long>, 8>(c, f.count, f.lds); break;
       default: return FTAR_ERR_UNSUPPORTED;
     }
     break;
-  case FTAR_MAX: e = tr_min_max<true>(dt, lds, srcs, k, dst, count, s); break;
-  case FTAR_MIN: e = tr_min_max<false>(dt, lds, srcs, k, dst, count, s); break;
+  case FTAR_MAX: e = min_max<true>(f); break;
+  case FTAR_MIN: e = min_max<false>(f); break;
   case FTAR_AVG: break;  // refused above
   }
   FTAR_CHECK_HIP(e);
