@@ -5,6 +5,7 @@
 // reduce_impl.h are instantiated here from the same templates; launch_gather (variant 90) and
 // launch_reduce (the nested-fold A/B) are the product's own, linked from libftar.so.
 #include "cast_impl.h"
+#include "mx_impl.h"
 #include "reduce_impl.h"
 
 namespace ftar {
@@ -588,6 +589,28 @@ extern "C" ftar_status_t ftar_bench_cast_sr_words(const void* src, int src_dtype
   FTAR_CHECK_HIP((launch_cast_any<kCastU16, kCastU32, kCastLayout, SrWords>(
       src, (ftar_dtype_t)src_dtype, dst, (ftar_dtype_t)dst_dtype, count, scale, nullptr,
       static_cast<hipStream_t>(stream), SrWords::Arg{words, count})));
+  return FTAR_SUCCESS;
+}
+
+// The production stochastic MX quantize (mx_impl.h: same kernels, family choice and grids) on an explicit array of
+// words, words[i] for element i of the call, in place of the generator: tests/test_gpu_mx_sr.py.  mode: ftar_mx_mode_t.
+extern "C" ftar_status_t ftar_bench_mx_quantize_sr_words(const void* src, int src_dtype, void* dst, int dst_dtype,
+                                                         size_t count, int mode, int headroom, unsigned char* scales,
+                                                         const unsigned* words, void* stream) {
+  using namespace ftar;
+  if (!is_cast_wide((ftar_dtype_t)src_dtype) || !is_f8((ftar_dtype_t)dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (mode != FTAR_MX_COMPUTE && mode != FTAR_MX_GIVEN) return FTAR_ERR_INVALID_ARG;
+  if (headroom < 0 || headroom > 31 || (mode == FTAR_MX_GIVEN && headroom != 0)) return FTAR_ERR_INVALID_ARG;
+  if (!src || !dst || !scales || !words || !count) return FTAR_ERR_INVALID_ARG;
+  const SrWords::Arg rnd{words, count};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  FTAR_CHECK_HIP(mx_with_pair((ftar_dtype_t)src_dtype, (ftar_dtype_t)dst_dtype, [&](auto w, auto f) {
+    using W = decltype(w);
+    using F = decltype(f);
+    return mode == FTAR_MX_GIVEN
+               ? launch_mx_quant_pair<W, F, kMxGiven, SrWords>(src, dst, scales, count, headroom, s, rnd)
+               : launch_mx_quant_pair<W, F, kMxCompute, SrWords>(src, dst, scales, count, headroom, s, rnd);
+  }));
   return FTAR_SUCCESS;
 }
 

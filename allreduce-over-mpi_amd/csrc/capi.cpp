@@ -299,6 +299,21 @@ ftar_status_t ftar_mx_quantize(const void* src, ftar_dtype_t src_dtype, void* ds
                                   static_cast<hipStream_t>(stream));
 }
 
+// The stochastic quantize: the header's refusal order -- pair, mode, headroom, seed (at count == 0 too), pointers --
+// before any device work.
+ftar_status_t ftar_mx_quantize_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                                  size_t count, int mode, int headroom, uint8_t* scales, const uint64_t* seed,
+                                  uint64_t offset, void* stream) {
+  if (!ftar::mx_pair_supported(src_dtype, dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (mode != FTAR_MX_COMPUTE && mode != FTAR_MX_GIVEN) return FTAR_ERR_INVALID_ARG;
+  if (headroom < 0 || headroom > 31 || (mode == FTAR_MX_GIVEN && headroom != 0)) return FTAR_ERR_INVALID_ARG;
+  if (!seed || (reinterpret_cast<uintptr_t>(seed) & 7)) return FTAR_ERR_INVALID_ARG;
+  if (count && (!src || !dst || !scales)) return FTAR_ERR_INVALID_ARG;
+  return ftar::launch_mx_quantize_sr(src, src_dtype, dst, dst_dtype, count, mode == FTAR_MX_GIVEN, headroom, scales,
+                                     reinterpret_cast<const unsigned long long*>(seed), offset,
+                                     static_cast<hipStream_t>(stream));
+}
+
 ftar_status_t ftar_mx_dequantize(const void* src, ftar_dtype_t src_dtype, const uint8_t* scales, void* dst,
                                  ftar_dtype_t dst_dtype, size_t count, void* stream) {
   if (!ftar::mx_pair_supported(dst_dtype, src_dtype)) return FTAR_ERR_UNSUPPORTED;

@@ -271,6 +271,11 @@ ftar_status_t launch_mx_scales(const void* src, ftar_dtype_t src_dt, ftar_dtype_
                                unsigned char* scales, hipStream_t stream);
 ftar_status_t launch_mx_quantize(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t f8_dt, size_t count,
                                  bool given, int headroom, unsigned char* scales, hipStream_t stream);
+// ftar_mx_quantize_sr's: the same with the stochastic narrowing sr_dst(p, U(*seed, offset + i)), i the call's element
+// index whichever kernel family, tile or lane stores it; the seed is read on the device.
+ftar_status_t launch_mx_quantize_sr(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t f8_dt, size_t count,
+                                    bool given, int headroom, unsigned char* scales, const unsigned long long* seed,
+                                    unsigned long long offset, hipStream_t stream);
 ftar_status_t launch_mx_dequantize(const void* src, ftar_dtype_t f8_dt, const unsigned char* scales, void* dst,
                                    ftar_dtype_t dst_dt, size_t count, hipStream_t stream);
 

@@ -23,6 +23,11 @@
 // zeros (the max's identity), the lane on the partial last vector moves its elements one by one, and its scale
 // bytes go out one per group leader.  The vector kernels need src and dst 16-byte aligned (a block then starts a vector); any other
 // call runs the element-wise kernels, one block per lane, which store the same bits.
+//
+// ftar_mx_quantize_sr: the quantize side's narrowing takes cast_impl.h's rounding policy (RneRound, SrGen, SrWords);
+// the stochastic kernels (mx_quant_vec_sr_kernel, mx_quant_elem_sr_kernel; kMxCompute and kMxGiven) hash the call
+// index of every element they store, so the word of element i is U(*seed, offset + i) in either family, any tile
+// and any lane.  The scale bytes are computed before the narrowing and do not depend on it.
 #pragma once
 #include "cast_impl.h"
 
@@ -156,9 +161,13 @@ __device__ __forceinline__ void mx_store_part(S* p, u32x4 v, int m) {
 }
 
 // ---- quantize side: one workgroup tile of NI x BS wide vectors starting at vector q0 ------------------------
-template <class Src, class Dst, int NI, int BS, int MODE, bool GUARD>
+// rd: the narrowing's rounding (cast_impl.h); its words are indexed by the call index of each chunk's first element,
+// q * EPV for vector q's chunk 0 -- in the unguarded and the guarded tile, on the partial last vector (whose spare
+// elements' words are computed and dropped with their bytes) and in every pass of the grid-stride loop alike.
+template <class Src, class Dst, int NI, int BS, int MODE, bool GUARD, class Rd = RneRound>
 __device__ __forceinline__ void mx_quant_tile(const typename Src::S* src, unsigned char* dst, unsigned char* scales,
-                                              size_t q0, size_t count, int headroom, int W) {
+                                              size_t q0, size_t count, int headroom, int W,
+                                              const Rd& rd = Rd{typename Rd::Arg{}}) {
   using S = typename Src::S;
   constexpr int EPV = 16 / sizeof(S);        // elements of a wide vector: 4 / 8
   constexpr int LPB = kMxBlock / EPV;        // lanes of a block: 8 / 4
@@ -195,10 +204,9 @@ __device__ __forceinline__ void mx_quant_tile(const typename Src::S* src, unsign
     }
     if constexpr (MODE != kMxScales) {
       const float r = __uint_as_float(mx_q_bits(s));
-      const RneRound rd{RneRound::Arg{}};
       u32x4 out = {0, 0, 0, 0};
-      if constexpr (NC == 2) cast_chunks<Src, Dst, 0, 2>(&in[i], &out, r, rd, 0);
-      else cast_put<Dst>(&out, 0, cast_mul(__builtin_bit_cast(f32x4, in[i]), r), rd, 0);
+      if constexpr (NC == 2) cast_chunks<Src, Dst, 0, 2>(&in[i], &out, r, rd, q * EPV);
+      else cast_put<Dst>(&out, 0, cast_mul(__builtin_bit_cast(f32x4, in[i]), r), rd, q * EPV);
       if (!GUARD || q < nfull) {
         if constexpr (NC == 1) __builtin_nontemporal_store(out.x, reinterpret_cast<unsigned*>(dst) + q);
         else __builtin_nontemporal_store(u32x2{out.x, out.y}, reinterpret_cast<u32x2*>(dst) + q);
@@ -224,6 +232,28 @@ __global__ void __launch_bounds__(BS)
     else
       mx_quant_tile<Src, Dst, NI, BS, MODE, true>(static_cast<const S*>(src), static_cast<unsigned char*>(dst), scales,
                                                   t * T, count, headroom, W);
+  }
+}
+// The stochastic twin (kMxCompute, kMxGiven): the same loop over the same tiles, the words' source (Rd: SrGen /
+// SrWords) built from its argument as cast_vec_sr_kernel's is.  A kernel of its own and not a shared body: the
+// round-to-nearest kernel above keeps its symbol, its arguments and, instruction for instruction, its code (a
+// shared always-inline body between the two changed its block order and address arithmetic).
+template <class Rd, class Src, class Dst, int NI, int BS, int MODE>
+__global__ void __launch_bounds__(BS)
+    mx_quant_vec_sr_kernel(const void* src, void* dst, unsigned char* scales, size_t count, int headroom, int W,
+                           typename Rd::Arg rnd) {
+  static_assert(MODE != kMxScales, "scale bytes do not depend on the rounding");
+  using S = typename Src::S;
+  constexpr size_t EPV = 16 / sizeof(S), T = (size_t)NI * BS;
+  const size_t nq = (count + EPV - 1) / EPV, full = (count / EPV) / T, tiles = (nq + T - 1) / T;
+  const Rd rd(rnd);
+  for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {   // uniform over the workgroup
+    if (t < full)
+      mx_quant_tile<Src, Dst, NI, BS, MODE, false>(static_cast<const S*>(src), static_cast<unsigned char*>(dst), scales,
+                                                   t * T, count, headroom, W, rd);
+    else
+      mx_quant_tile<Src, Dst, NI, BS, MODE, true>(static_cast<const S*>(src), static_cast<unsigned char*>(dst), scales,
+                                                  t * T, count, headroom, W, rd);
   }
 }
 
@@ -252,6 +282,35 @@ __global__ void __launch_bounds__(kThreads)
       const float r = __uint_as_float(mx_q_bits(sb));
       for (int j = 0; j < m; ++j) d[e0 + j] = Dst::narrow(cast_mul(Src::widen(s[e0 + j]), r));
     }
+  }
+}
+// its stochastic twin, a kernel of its own for the reason above
+template <class Rd, class Src, class Dst, int MODE>
+__global__ void __launch_bounds__(kThreads)
+    mx_quant_elem_sr_kernel(const void* src, void* dst, unsigned char* scales, size_t count, int headroom,
+                            typename Rd::Arg rnd) {
+  static_assert(MODE != kMxScales, "scale bytes do not depend on the rounding");
+  using S = typename Src::S;
+  constexpr int kEmax = std::is_same_v<Dst, CastE5M2> ? 15 : 8;
+  const S* s = static_cast<const S*>(src);
+  unsigned char* d = static_cast<unsigned char*>(dst);
+  const Rd rd(rnd);
+  const size_t nblocks = (count + kMxBlock - 1) / kMxBlock, stride = (size_t)gridDim.x * kThreads;
+  for (size_t b = (size_t)blockIdx.x * kThreads + threadIdx.x; b < nblocks; b += stride) {
+    const size_t e0 = b * kMxBlock;
+    const int m = count - e0 < (size_t)kMxBlock ? (int)(count - e0) : kMxBlock;
+    unsigned sb;
+    if constexpr (MODE == kMxGiven) {
+      sb = scales[b];
+    } else {
+      unsigned k = 0;
+      for (int j = 0; j < m; ++j) k = umax(k, MxPeak<Src>::s_key(s[e0 + j]));
+      sb = mx_scale_of(MxPeak<Src>::bits(k), kEmax, headroom);
+      scales[b] = (unsigned char)sb;
+    }
+    const float r = __uint_as_float(mx_q_bits(sb));
+    for (int j = 0; j < m; ++j)   // element e0 + j of the call takes word e0 + j
+      d[e0 + j] = SrFmt<std::is_same_v<Dst, CastE5M2>>::narrow(cast_mul(Src::widen(s[e0 + j]), r), rd.word(e0 + j));
   }
 }
 
@@ -336,11 +395,20 @@ inline unsigned mx_vec_blocks(size_t count, size_t elems_per_tile) {
 // Wide vectors per lane and pass (NI): 4 for both widths -- 16 f32 or 32 16-bit elements in flight per lane.
 constexpr int kMxNI = 4;
 
-template <class Src, class Dst, int MODE>
+template <class Src, class Dst, int MODE, class Rd = RneRound>
 hipError_t launch_mx_quant_pair(const void* src, void* dst, unsigned char* scales, size_t count, int headroom,
-                                hipStream_t s) {
+                                hipStream_t s, typename Rd::Arg rnd = {}) {
   constexpr size_t EPV = 16 / sizeof(typename Src::S);
-  if (mx_aligned16(src) && (MODE == kMxScales || mx_aligned16(dst))) {
+  if constexpr (Rd::kSr) {   // the same choice of family and the same grids, the stochastic twins
+    if (mx_aligned16(src) && mx_aligned16(dst)) {
+      FTAR_LAUNCH((mx_quant_vec_sr_kernel<Rd, Src, Dst, kMxNI, kMxThreads, MODE>),
+                  dim3(mx_vec_blocks(count, kMxNI * kMxThreads * EPV)), dim3(kMxThreads), 0, s, src, dst, scales, count,
+                  headroom, mx_scale_store_width<kMxBlock / (int)EPV>(scales), rnd);
+    } else {
+      FTAR_LAUNCH((mx_quant_elem_sr_kernel<Rd, Src, Dst, MODE>), dim3(elem_blocks((count + kMxBlock - 1) / kMxBlock)),
+                  dim3(kThreads), 0, s, src, dst, scales, count, headroom, rnd);
+    }
+  } else if (mx_aligned16(src) && (MODE == kMxScales || mx_aligned16(dst))) {
     FTAR_LAUNCH((mx_quant_vec_kernel<Src, Dst, kMxNI, kMxThreads, MODE>),
                 dim3(mx_vec_blocks(count, kMxNI * kMxThreads * EPV)), dim3(kMxThreads), 0, s, src, dst, scales, count,
                 headroom, mx_scale_store_width<kMxBlock / (int)EPV>(scales));

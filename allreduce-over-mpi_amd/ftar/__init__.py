@@ -133,6 +133,7 @@ _lib.ftar_cast_scaled.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, _vp]
 _lib.ftar_cast_scaled_sr.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, ctypes.c_uint64, _vp, _vp]
 _lib.ftar_mx_scales.argtypes = [_vp, _int, _int, _sz, _int, _vp, _vp]
 _lib.ftar_mx_quantize.argtypes = [_vp, _int, _vp, _int, _sz, _int, _int, _vp, _vp]
+_lib.ftar_mx_quantize_sr.argtypes = [_vp, _int, _vp, _int, _sz, _int, _int, _vp, _vp, ctypes.c_uint64, _vp]
 _lib.ftar_mx_dequantize.argtypes = [_vp, _int, _vp, _vp, _int, _sz, _vp]
 _lib.ftar_topo_parse.argtypes = [ctypes.c_char_p, ctypes.c_char_p, _int, ctypes.POINTER(Topo)]
 _lib.ftar_topo_from_env.argtypes = [_int, _sz, ctypes.POINTER(Topo)]
@@ -228,7 +229,7 @@ _bench_lib = None
 def bench_lib():
     """libftar_bench.so: the A/B kernel variants (ftar_debug_reduce_variant, ftar_debug_reduce_nested_lds) and
     kernel test hooks (ftar_debug_bf16_cvt_check, ftar_debug_f16_cvt_check, ftar_debug_f8_cvt_check,
-    ftar_bench_cast_sr_words, ftar_bench_sr_sweep) that tools/kbench*.py and the tests load; kept out of the
+    ftar_bench_cast_sr_words, ftar_bench_mx_quantize_sr_words, ftar_bench_sr_sweep) that tools/kbench*.py and the tests load; kept out of the
     product library, which holds only the kernels the engine dispatches."""
     global _bench_lib
     if _bench_lib is None:
@@ -449,11 +450,21 @@ def mx_scales(src, scales, count, src_dtype, fp8_dtype, headroom=0, stream=None)
                                _stream(stream)), "ftar_mx_scales")
 
 
-def mx_quantize(src, dst, scales, count, src_dtype, dst_dtype, mode="compute", headroom=0, stream=None):
+def mx_quantize(src, dst, scales, count, src_dtype, dst_dtype, mode="compute", headroom=0, stream=None,
+                rounding="nearest", seed=None, offset=0):
     """dst[i] = (src[i] as fp32 * 2^(127 - scales[i // 32])) rounded to the fp8 dst_dtype (ftar_mx_quantize), no
     saturation.  mode="compute": one pass that writes scales (mx_scales' bytes) and dst; mode="given": reads
     scales, device memory an earlier kernel on the stream may have written (headroom must be 0).  Any other mode
-    raises ValueError before any device work."""
+    raises ValueError before any device work.
+    rounding="stochastic" (ftar_mx_quantize_sr): the scale bytes are the same, and each scaled element goes to one
+    of its two fp8 neighbours with the expectation of the product, decided by a 32-bit word that is a pure function
+    of the 64-bit value at `seed` (device memory, 8-byte aligned: a pointer or a 1-element int64 tensor on src's
+    device) and of the global element index offset + i; cast_scaled's words, ValueErrors included."""
+    if _rounding(rounding, seed):
+        _check(_lib.ftar_mx_quantize_sr(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _mx_mode(mode),
+                                        int(headroom), _ptr(scales), _ptr(seed), int(offset) & 0xFFFFFFFFFFFFFFFF,
+                                        _stream(stream)), "ftar_mx_quantize_sr")
+        return
     _check(_lib.ftar_mx_quantize(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _mx_mode(mode),
                                  int(headroom), _ptr(scales), _stream(stream)), "ftar_mx_quantize")
 
@@ -480,13 +491,20 @@ def _mx_tensors(wide, f8, scales):
         raise ValueError(f"src, dst and scales are on {wide.device}, {f8.device} and {scales.device}")
 
 
-def mx_quantize_tensor(src, dst, scales, mode="compute", headroom=0, stream=None):
+def mx_quantize_tensor(src, dst, scales, mode="compute", headroom=0, stream=None, rounding="nearest", seed=None,
+                       offset=0):
     """mx_quantize on tensors: src f32 / bf16 / f16, dst torch.float8_e4m3fn / torch.float8_e5m2 of equal numel,
     scales torch.uint8 with at least mx_nblocks(src.numel()) elements.  ValueError unless all three are contiguous
-    and on one device and the mode is known.  Returns dst."""
+    and on one device, the mode and the rounding are known and, with rounding="stochastic", seed is a 1-element
+    int64 tensor on that device.  Returns dst."""
+    import torch
     _mx_mode(mode)
+    stochastic = _rounding(rounding, seed)
     _mx_tensors(src, dst, scales)
-    mx_quantize(src, dst, scales, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), mode, headroom, stream)
+    if stochastic:
+        _one_elem(seed, "seed", src.device, torch.int64)
+    mx_quantize(src, dst, scales, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), mode, headroom, stream,
+                rounding, seed if stochastic else None, offset)
     return dst
 
 

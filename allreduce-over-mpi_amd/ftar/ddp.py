@@ -38,7 +38,8 @@ quantize with a power-of-two scale (ftar_cast_scaled, or with rounding="stochast
 with op="avg" and amax, dequantize; the scale follows the amax one step behind (next_fp8_scale), on the device.
 mx_compress_hook (with MxCompressState) is the block-scaled (MX) form of that wire: one power-of-two scale byte per
 32 elements, agreed among the ranks in the same step by a MAX AllReduce of the bytes, so small layers of a bucket
-keep their bits and no step overflows the wire; no scale policy to run.
+keep their bits and no step overflows the wire; no scale policy to run.  It takes rounding="stochastic" too
+(ftar_mx_quantize_sr), with Fp8CompressState's seed and offset.
 
 The reference reduces MPI buffers (MPI_Allreduce_FT, mpi_mod.hpp:1723-1778); a DDP bucket is the same call on
 a device tensor, in place (`sendbuf = MPI_IN_PLACE`).
@@ -279,14 +280,30 @@ class MxCompressState:
     bucket's device it keeps a grow-only fp8 wire buffer, a grow-only uint8 scale buffer (one byte per 32 elements)
     and a 1-element fp32 flag.  found_inf() is 1.0 once any reduced scale byte since reset() was 255 -- a block that
     held an inf or a NaN on some rank -- and stays on the device.  There is no scale policy, no update_scale() and no
-    amax: every block's scale is computed from this step's data.  No host synchronisation anywhere."""
+    amax: every block's scale is computed from this step's data.  No host synchronisation anywhere.
 
-    def __init__(self, comm, fmt="e4m3", topo=None, lonely=0, headroom=0):
+    rounding="stochastic": step (3) of the hook rounds each scaled element to one of its two fp8 neighbours with the
+    expectation of the scaled value (ftar_mx_quantize_sr); the scale bytes, and so steps (1), (2), (4), (5) and
+    found_inf(), do not change.  As in Fp8CompressState the state then keeps `seed`, a 1-element int64 device tensor
+    derived once on the host from (seed, comm.rank) through rank_seed, and `offset`, a host-side count of the elements
+    quantized so far, which grows by the bucket's numel per bucket and is never reset, so no two buckets of a run
+    share a word.  Under graph capture the offset is baked into the captured kernel: a caller who replays a captured
+    hook must change state.seed on the device between replays (e.g. state.seed.add_(1)), or every replay rounds the
+    same way.  The default, "nearest", keeps no seed and stores the bits it always stored."""
+
+    def __init__(self, comm, fmt="e4m3", topo=None, lonely=0, headroom=0, rounding="nearest", seed=0):
         if fmt not in FP8_MAX:
             raise ValueError(f"fmt must be 'e4m3' or 'e5m2', not {fmt!r}")
         if isinstance(headroom, bool) or not isinstance(headroom, int) or not 0 <= headroom <= 31:
             raise ValueError(f"headroom must be an integer in 0..31, not {headroom!r}")
+        if rounding not in ftar.ROUNDINGS:
+            raise ValueError(f"rounding must be 'nearest' or 'stochastic', not {rounding!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an integer, not {seed!r}")
         self.comm, self.fmt, self.topo, self.lonely, self.headroom = comm, fmt, topo, lonely, headroom
+        self.rounding, self.base_seed = rounding, seed
+        self.seed = None      # stochastic: the rank's device seed, created on the first bucket's device
+        self.offset = 0
         self.wire_dtype = _FP8_DTYPE[fmt]
         self._wire = self._scales = self._inf = None
         self.calls = 0
@@ -294,6 +311,9 @@ class MxCompressState:
     def _on(self, device, n):
         if self._inf is None:
             self._inf = torch.zeros(1, dtype=torch.float32, device=device)
+            if self.rounding == "stochastic":
+                word = rank_seed(self.base_seed, getattr(self.comm, "rank", 0))
+                self.seed = torch.tensor([word - (1 << 64) if word >> 63 else word], dtype=torch.int64, device=device)
         if self._wire is None or self._wire.numel() < n:
             self._wire = torch.empty(n, dtype=torch.uint8, device=device)
             self._scales = torch.empty(ftar.mx_nblocks(n), dtype=torch.uint8, device=device)
@@ -317,7 +337,8 @@ def mx_compress_hook(state, bucket):
     (1) ftar_mx_scales: each block's scale byte from this rank's bucket, state.headroom binades above its peak;
     (2) the bytes' in-place AllReduce of u8 with op="max": every rank now holds each block's largest scale, and 255
         (NaN) wherever any rank's block held an inf or a NaN -- a NaN byte wins the unsigned MAX by itself;
-    (3) ftar_mx_quantize with those given scales: two fp8 blocks that share a scale byte sum as plain fp8 values;
+    (3) ftar_mx_quantize with those given scales: two fp8 blocks that share a scale byte sum as plain fp8 values
+        (with state.rounding == "stochastic" ftar_mx_quantize_sr on state.seed at the running state.offset);
     (4) the wire's in-place AllReduce with op="avg";
     (5) ftar_mx_dequantize back into the bucket; a block whose byte is 255 comes back all NaN on every rank, and
         state.found_inf() turns 1.0.
@@ -348,7 +369,12 @@ def mx_compress_hook(state, bucket):
     dt, f8 = ftar._dt(str(t.dtype)), ftar._dt(state.wire_dtype)
     ftar.mx_scales(t, scales, n, dt, f8, headroom=state.headroom, stream=stream)
     state.comm.allreduce(None, scales, nb, "u8", "max", topo_=state.topo, lonely=state.lonely, stream=stream)
-    ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream)
+    if state.rounding == "stochastic":
+        ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream, rounding="stochastic",
+                         seed=state.seed, offset=state.offset)
+        state.offset += n
+    else:
+        ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream)
     state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream)
     ftar.mx_dequantize(wire, scales, t, n, f8, dt, stream=stream)
     torch.maximum(state._inf, (scales[:nb].max() == 255).to(torch.float32).reshape(1), out=state._inf)

@@ -82,6 +82,7 @@ typedef enum {
  *   cast (ftar_cast_scaled): f32 bf16 f16 -> f8e4m3 f8e5m2 and back, times a device scale; every other pair is refused.
  *   stochastic cast (ftar_cast_scaled_sr): f32 bf16 f16 -> f8e4m3 f8e5m2 only; the way back and every other pair is refused.
  *   MX casts (ftar_mx_scales, ftar_mx_quantize: f32 bf16 f16 -> f8e4m3 f8e5m2; ftar_mx_dequantize: the way back); every other pair is refused.
+ *   stochastic MX quantize (ftar_mx_quantize_sr): f32 bf16 f16 -> f8e4m3 f8e5m2, both modes; every other pair is refused.
  *
  * The 16-bit floats (no reference; bf16 and IEEE binary16 follow the same rules): a SUM accumulates in fp32,
  * left to right, and rounds once to nearest even per reduce call -- once for a flat fold, once per hop on the
@@ -224,7 +225,28 @@ typedef enum {
  * an element-wise family (one block per lane) that stores the same bits.  Each call enqueues kernels only -- no
  * memset, no host read, no synchronisation -- so it captures into a HIP graph and the scales may come from an
  * earlier kernel on the stream.  Splitting [0, n) at a multiple of 32 into two calls stores the same bits.  src,
- * dst and scales must not overlap.  MXFP6 / MXFP4 and stochastic rounding of the MX quantize are not covered.
+ * dst and scales must not overlap.
+ *   Stochastic quantize (ftar_mx_quantize_sr): ftar_mx_quantize with the narrowing of the stochastic-rounding
+ *   paragraph above.  Element i of the call stores sr_dst(mul_rn_f32(widen(src[i]), q(s)), U(*seed, offset + i)), s
+ *   the scale byte of i's block, sr_dst and U exactly those of that paragraph: block b of a call stores what
+ *   ftar_cast_scaled_sr stores for that block with r = q(s_b) and offset + 32b.  Everything else is
+ *   ftar_mx_quantize's -- scale bytes, q(s), modes, headroom, the six pairs.  The scale bytes do not depend on the
+ *   rounding: FTAR_MX_COMPUTE writes the bytes ftar_mx_scales writes, and stores the payload that ftar_mx_scales
+ *   followed by ftar_mx_quantize_sr(FTAR_MX_GIVEN) stores given the same seed and offset.  A block with s = 255
+ *   (q = 1.0f) has the stochastic plain cast as its payload.  Under FTAR_MX_COMPUTE a finite block still stores no
+ *   NaN and no inf, for every word: its scaled peak is at most the format's largest finite value, which is
+ *   representable and so stored unchanged, and the carry of a smaller magnitude cannot pass it.  FTAR_MX_GIVEN with
+ *   foreign scales may overflow as the RNE quantize does, with ftar_cast_scaled_sr's probabilities.  The word
+ *   depends only on *seed (device memory, 8-byte aligned, read by the kernel on the stream, never by the host) and
+ *   on offset + i (mod 2^64): not on alignment, on the vector or element-wise family that ran, on the grid or the
+ *   tile, or on how the call was split -- splitting [0, n) at a multiple of 32 into two calls, the second with
+ *   offset + cut, stores the one-call bits.  Refusals, in this order, all before any device work and leaving every
+ *   buffer untouched: an unsupported pair FTAR_ERR_UNSUPPORTED; then FTAR_ERR_INVALID_ARG for a mode outside the
+ *   enum; a headroom outside 0..31 or != 0 with FTAR_MX_GIVEN; a NULL seed or one not 8-byte aligned (at count == 0
+ *   too, as in ftar_cast_scaled_sr); a NULL src / dst / scales with count > 0.  count == 0 otherwise succeeds and
+ *   writes nothing.  The call enqueues kernels only, so it captures into a HIP graph, and a replay follows whatever
+ *   the seed word, the source and the scales hold on the device at that time.
+ * MXFP6 / MXFP4 are not covered.
  * The MPI drop-in (ftar_mpi.h) keeps the reference's datatype and op list: none of these extensions. */
 
 typedef enum {
@@ -322,6 +344,12 @@ ftar_status_t ftar_mx_scales(const void* src, ftar_dtype_t src_dtype, ftar_dtype
  * possibly written by an earlier kernel on the stream; headroom must be 0) and writes dst[]. */
 ftar_status_t ftar_mx_quantize(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
                                size_t count, int mode, int headroom, uint8_t* scales, void* stream);
+/* ftar_mx_quantize with stochastic rounding (the MX paragraph's stochastic quantize): element i takes the word
+ * U(*seed, offset + i).  seed: one uint64_t in device memory on the current device, 8-byte aligned, read by the
+ * kernel; offset: the global index of element 0 -- a running offset over consecutive calls never reuses a word. */
+ftar_status_t ftar_mx_quantize_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                                  size_t count, int mode, int headroom, uint8_t* scales,
+                                  const uint64_t* seed, uint64_t offset, void* stream);
 /* dst[i] = round_to_dst(fp32(src[i]) x 2^(scales[i / 32] - 127)), src fp8, dst f32 / bf16 / f16. */
 ftar_status_t ftar_mx_dequantize(const void* src, ftar_dtype_t src_dtype, const uint8_t* scales, void* dst,
                                  ftar_dtype_t dst_dtype, size_t count, void* stream);

@@ -11,7 +11,10 @@ its slowest rank.  The same on a --small-elems bucket shows the fixed cost of th
 A ONE-GPU PROXY: all ranks share one device and one HBM and the "wire" is device copies, so no number from this
 tool is an xGMI number -- on a node the wire's bytes cross links that are 10-20x slower than HBM while the three
 casts stay local.  Nobody has measured this hook across GPUs.
-python tools/hook_mx.py [--ranks 8] [--elems 67108864] [--small-elems 2048] [--rounds 7] [--topo 8] [--fmt e4m3]"""
+--rounding stochastic runs the "mx" and "mx-steps" modes (and the fp8 hook) with stochastic rounding at the quantize;
+--rounding both adds the mode "mx-sr" next to "mx", interleaved in the same run, and prints its ratio.
+python tools/hook_mx.py [--ranks 8] [--elems 67108864] [--small-elems 2048] [--rounds 7] [--topo 8] [--fmt e4m3]
+                        [--rounding nearest|stochastic|both]"""
 import argparse
 import json
 import os
@@ -33,9 +36,11 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--topo", default=None, help="FT_TOPO syntax; default: the execution model's choice")
 ap.add_argument("--fmt", default="e4m3")
 ap.add_argument("--headroom", type=int, default=0)
+ap.add_argument("--rounding", default="nearest", choices=("nearest", "stochastic", "both"))
 a = ap.parse_args()
 P = a.ranks
-MODES = ("mx", "mx-steps", "fp8", "bf16")
+ROUNDING = "stochastic" if a.rounding == "stochastic" else "nearest"
+MODES = ("mx", "mx-steps", "fp8", "bf16") + (("mx-sr",) if a.rounding == "both" else ())
 STEPS = ("scales", "allreduce_u8_max", "quantize_given", "allreduce_f8_avg", "dequantize")
 
 
@@ -49,11 +54,14 @@ class Bucket:
 
 group = ftar.Comm.init_local(P)
 streams = [torch.cuda.Stream() for _ in range(P)]
-states = {"mx": [ftar.ddp.MxCompressState(group[r], fmt=a.fmt, topo=a.topo, headroom=a.headroom) for r in range(P)],
-          "fp8": [ftar.ddp.Fp8CompressState(group[r], fmt=a.fmt, topo=a.topo) for r in range(P)],
+states = {"mx": [ftar.ddp.MxCompressState(group[r], fmt=a.fmt, topo=a.topo, headroom=a.headroom, rounding=ROUNDING)
+                 for r in range(P)],
+          "mx-sr": [ftar.ddp.MxCompressState(group[r], fmt=a.fmt, topo=a.topo, headroom=a.headroom,
+                                             rounding="stochastic") for r in range(P)],
+          "fp8": [ftar.ddp.Fp8CompressState(group[r], fmt=a.fmt, topo=a.topo, rounding=ROUNDING) for r in range(P)],
           "bf16": [ftar.ddp.HookState(group[r], topo=a.topo, average="fused") for r in range(P)]}
 states["mx-steps"] = states["mx"]
-hooks = {"mx": ftar.ddp.mx_compress_hook, "fp8": ftar.ddp.fp8_compress_hook, "bf16": ftar.ddp.allreduce_hook}
+hooks = {"mx": ftar.ddp.mx_compress_hook, "mx-sr": ftar.ddp.mx_compress_hook, "fp8": ftar.ddp.fp8_compress_hook, "bf16": ftar.ddp.allreduce_hook}
 
 
 def mx_steps(state, t, stream):
@@ -67,7 +75,12 @@ def mx_steps(state, t, stream):
     ev[1].record()
     state.comm.allreduce(None, scales, nb, "u8", "max", topo_=state.topo, lonely=state.lonely, stream=stream)
     ev[2].record()
-    ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream)
+    if state.rounding == "stochastic":
+        ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream, rounding="stochastic",
+                         seed=state.seed, offset=state.offset)
+        state.offset += n
+    else:
+        ftar.mx_quantize(t, wire, scales, n, dt, f8, mode="given", stream=stream)
     ev[3].record()
     state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream)
     ev[4].record()
@@ -124,6 +137,7 @@ def measure(elems):
             res[m].append(one_call(m))
     n = elems
     print(json.dumps({"ranks": P, "elems": n, "bucket_KiB": n * 2 / 2**10, "wire": a.fmt, "headroom": a.headroom,
+                      "rounding": a.rounding,
                       "wire_bytes_per_rank": n + 2 * ftar.mx_nblocks(n), "bf16_bytes_per_rank": 2 * n,
                       "rounds": a.rounds, "last_exec": execs,
                       "note": "one-GPU proxy (in-process group): no xGMI number"}))
@@ -143,6 +157,9 @@ def measure(elems):
         med[m] = statistics.median(worst)
         print(json.dumps({"mode": m, "ms_slowest_rank_med": round(med[m], 4), "ms_slowest_rank_min": round(min(worst), 4),
                           "ms_slowest_rank_max": round(max(worst), 4)}), flush=True)
+    if "mx-sr" in med:
+        print(json.dumps({"mx-sr_vs": "mx", "ms_delta": round(med["mx-sr"] - med["mx"], 4),
+                          "ratio": round(med["mx-sr"] / med["mx"], 4)}), flush=True)
     for other in ("fp8", "bf16"):
         print(json.dumps({"mx_vs": other, "ms_delta": round(med["mx"] - med[other], 4),
                           "ratio": round(med["mx"] / med[other], 4)}), flush=True)

@@ -13,9 +13,16 @@ of interleaved rounds with the slowest and fastest round next to it.  Labels:
   ...#2               a label again under a name of its own: the run's own spread between two labels of one kernel,
                       the margin of every comparison
 
-The last lines give each MX label's ratio to its pair's ftar_cast_scaled (medians; > 1 is faster).  Random bytes on
-all sides, so blocks hold NaN and inf too and scale bytes are any byte: the instructions do not care.
-python tools/mx_rates.py [--pairs f32>f8e4m3,...] [--rounds 5] [--reps 8]"""
+With --sr, for every quantize pair also:
+  f32>f8e4m3:mx-sr    ftar_mx_quantize_sr, FTAR_MX_COMPUTE
+  f32>f8e4m3:given-sr ftar_mx_quantize_sr, FTAR_MX_GIVEN
+  f32>f8e4m3:sr       ftar_cast_scaled_sr of the pair: the stochastic yardstick
+
+The last lines give each MX label's ratio to its pair's ftar_cast_scaled (medians; > 1 is faster), and with --sr each
+stochastic MX label's ratio to its two yardsticks of the same run: the round-to-nearest label of its pair and mode,
+and ftar_cast_scaled_sr of its pair.  Random bytes on all sides, so blocks hold NaN and inf too and scale bytes are
+any byte: the instructions do not care.
+python tools/mx_rates.py [--pairs f32>f8e4m3,...] [--rounds 5] [--reps 8] [--sr]"""
 import argparse
 import json
 import os
@@ -33,6 +40,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--pairs", default=",".join(ALL))
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=8)
+ap.add_argument("--sr", action="store_true", help="also the stochastic quantizes of every quantize pair")
 a = ap.parse_args()
 NB = 256 << 20
 S = 4
@@ -40,6 +48,7 @@ bufs = [[torch.randint(0, 256, (NB,), dtype=torch.uint8, device="cuda") for _ in
 scs = [torch.randint(0, 256, (NB // 2 // 32,), dtype=torch.uint8, device="cuda") for _ in range(S)]
 stream = torch.cuda.current_stream()
 scale = torch.full((1,), 0.5, dtype=torch.float32, device="cuda")
+seed = torch.tensor([0x0123456789ABCDEF], dtype=torch.int64, device="cuda")
 
 
 def shape(pair):
@@ -58,6 +67,13 @@ def make(label):
     pair, _, kind = base.partition(":")
     s, d = pair.split(">")
     n, both, nb = shape(pair)
+    if kind == "sr":
+        return (lambda i: ftar.cast_scaled(bufs[i % S][0], bufs[i % S][1], n, s, d, scale=scale, stream=stream,
+                                           rounding="stochastic", seed=seed, offset=i * n)), both
+    if kind in ("mx-sr", "given-sr"):
+        mode = "compute" if kind == "mx-sr" else "given"
+        return (lambda i: ftar.mx_quantize(bufs[i % S][0], bufs[i % S][1], scs[i % S], n, s, d, mode=mode, stream=stream,
+                                           rounding="stochastic", seed=seed, offset=i * n)), both + nb
     if not kind:
         return (lambda i: ftar.cast_scaled(bufs[i % S][0], bufs[i % S][1], n, s, d, scale=scale, stream=stream)), both
     if kind == "scales":
@@ -75,7 +91,12 @@ for p in pairs:
     kinds = ("mx", "given", "scales") if p.split(">")[1] in F8 else ("mx",)
     mx_of[p] = [f"{p}:{k}" for k in kinds]
     labels += mx_of[p] + [p]
+sr_of = {p: [f"{p}:mx-sr", f"{p}:given-sr"] for p in pairs if a.sr and p.split(">")[1] in F8}
+for p, lbs in sr_of.items():
+    labels += lbs + [f"{p}:sr"]
 labels += [mx_of[pairs[0]][0] + "#2", pairs[0] + "#2"]
+if sr_of:
+    labels += [sr_of[next(iter(sr_of))][0] + "#2"]
 for mib in sorted({(shape(p)[1] + shape(p)[2]) >> 20 for p in pairs}):
     labels += [f"copy:{mib}", f"copy:{mib}#2"]
 runs = {lb: make(lb) for lb in labels}
@@ -105,3 +126,12 @@ for p in pairs:
                                                                                   statistics.median(res[lb]), 3),
                           "GBps_ratio_mx_over_cast": round((runs[lb][1] / statistics.median(res[lb])) /
                                                            (runs[p][1] / statistics.median(res[p])), 3)}), flush=True)
+for p, lbs in sr_of.items():
+    for lb in lbs:
+        t = statistics.median(res[lb])
+        print(json.dumps({"label": lb, "rate_over_rne": round(statistics.median(res[lb[:-3]]) / t, 3),
+                          "rne_label": lb[:-3],
+                          "rate_over_cast_scaled_sr": round((runs[lb][1] / t) / (runs[f"{p}:sr"][1] /
+                                                                                 statistics.median(res[f"{p}:sr"])), 3),
+                          "time_ratio_cast_scaled_sr_over_mx_sr": round(statistics.median(res[f"{p}:sr"]) / t, 3)}),
+              flush=True)
