@@ -72,9 +72,12 @@ ftar_status_t join_streams(hipStream_t stream, std::initializer_list<Join> joins
 // The reduce stream on `cus` of the device's CUs (0 or >= all: every CU), so
 // the transport's own kernels on the comm stream (RCCL's p2p kernels, the
 // local transport's copies) always find free CUs while a piece's fold runs:
-// the one-shot reduce grids otherwise fill every CU.  The CUs kept are spread
-// evenly over the mask (CU i is kept iff floor((i+1)*cus/N) > floor(i*cus/N)),
-// so every XCD keeps its share whichever way the mask bits map to XCDs.
+// the one-shot reduce grids otherwise fill every CU.  The driver deals the
+// mask's bits round-robin over the XCDs (bit i is a CU of XCD i % 8 on gfx950),
+// so the low `cus` bits give every XCD its share.  At least one CU per XCD is
+// kept (a smaller share runs on 8 CUs): a driver may refuse a mask that leaves
+// an XCD without a CU, and stream creation then fails with "out of memory" --
+// as it did for evenly spaced bits (every 4th bit is XCDs 3 and 7 only).
 // hipExtStreamCreateWithCUMask makes a blocking stream (it synchronises with
 // the legacy NULL stream) on a hardware queue of its own, the price of the knob.
 // Refused on RCCL communicators (Transport::masked_reduce_stream_ok): two runs
@@ -94,12 +97,13 @@ ftar_status_t set_reduce_cus(ftar_comm* c, int cus) {
   }
   if (cus == c->reduce_cus && c->red_s) return FTAR_SUCCESS;
   hipStream_t fresh = nullptr;
+  constexpr int kXcds = 8;
+  const int kept = cus ? std::min(total, std::max(cus, kXcds)) : total;
   if (cus == 0) {
     FTAR_CHECK_HIP(hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking));
   } else {
     std::vector<uint32_t> mask((size_t)(total + 31) / 32, 0u);
-    for (int i = 0; i < total; ++i)
-      if ((long)(i + 1) * cus / total > (long)i * cus / total) mask[(size_t)i / 32] |= 1u << (i % 32);
+    for (int i = 0; i < kept; ++i) mask[(size_t)i / 32] |= 1u << (i % 32);
     FTAR_CHECK_HIP(hipExtStreamCreateWithCUMask(&fresh, (uint32_t)mask.size(), mask.data()));
   }
   if (c->red_s) {
@@ -108,7 +112,7 @@ ftar_status_t set_reduce_cus(ftar_comm* c, int cus) {
   }
   c->red_s = fresh;
   c->reduce_cus = cus;
-  trace("rank %d: reduce stream on %d of %d CUs", c->rank, cus ? cus : total, total);
+  trace("rank %d: reduce stream on %d of %d CUs", c->rank, kept, total);
   return FTAR_SUCCESS;
 }
 

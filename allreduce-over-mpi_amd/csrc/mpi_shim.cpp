@@ -17,7 +17,8 @@
 //                                           communicator bootstrapped over MPI: peer forms)
 // Host buffers: MPI_Allreduce_FT_register pins a buffer the caller owns until
 // MPI_Allreduce_FT_unregister (like RCCL's user-buffer registration), so its
-// copies run at PCIe DMA speed; FTAR_MPI_REGISTER=1 additionally pins every
+// copies run at PCIe DMA speed (a buffer allocated page-locked, hipHostMalloc,
+// is pinned already and only recorded); FTAR_MPI_REGISTER=1 additionally pins every
 // buffer passed in, keeping at most FTAR_MPI_REGISTER_MAX (default 4) such
 // automatic registrations (least recently used evicted) -- the caller then
 // promises not to free a buffer it passed while it may still be registered.
@@ -63,7 +64,8 @@ std::set<Entry*> g_live;
 
 struct Registration {
   size_t bytes = 0;
-  bool automatic = false;  // FTAR_MPI_REGISTER=1 (evictable) vs MPI_Allreduce_FT_register
+  bool pinned_here = true;  // hipHostRegister'ed by us (false: the caller allocated it page-locked)
+  bool automatic = false;   // FTAR_MPI_REGISTER=1 (evictable) vs MPI_Allreduce_FT_register
   int in_use = 0;          // calls copying through it right now (never evicted then)
   uint64_t last_use = 0;
 };
@@ -287,6 +289,24 @@ std::map<uintptr_t, Registration>::iterator covering(const void* p, size_t bytes
   return a + bytes <= it->first + it->second.bytes ? it : g_registered.end();
 }
 
+// [p, p + bytes) is page-locked already (hipHostMalloc, or the caller's own hipHostRegister): both ends are
+// host memory the runtime knows
+bool already_pinned(const void* p, size_t bytes) {
+  for (const char* q : {static_cast<const char*>(p), static_cast<const char*>(p) + bytes - 1}) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, q) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    if (a.type != hipMemoryTypeHost) return false;
+  }
+  return true;
+}
+
+void unpin(const std::pair<const uintptr_t, Registration>& kv) {
+  if (kv.second.pinned_here) (void)hipHostUnregister(reinterpret_cast<void*>(kv.first));
+}
+
 bool auto_register() {
   static const bool on = getenv("FTAR_MPI_REGISTER") && atoi(getenv("FTAR_MPI_REGISTER")) != 0;
   return on;
@@ -315,7 +335,7 @@ uintptr_t acquire_pinned(const void* p, size_t bytes) {
             (lru == g_registered.end() || j->second.last_use < lru->second.last_use))
           lru = j;
       if (lru == g_registered.end()) return 0;  // all busy: this call copies pageable
-      (void)hipHostUnregister(reinterpret_cast<void*>(lru->first));
+      unpin(*lru);
       g_registered.erase(lru);
       --nauto;
     }
@@ -450,12 +470,16 @@ int MPI_Allreduce_FT_register(const void* buf, size_t bytes) {
     it->second.automatic = false;
     return MPI_SUCCESS;
   }
-  if (hipHostRegister(const_cast<void*>(buf), bytes, hipHostRegisterDefault) != hipSuccess) {
+  // memory the caller allocated page-locked (hipHostMalloc) is only recorded: the way to a pinned buffer on
+  // systems whose hipHostRegister cannot pin memory a program already has (MPI_ERR_OTHER there)
+  const bool pinned = already_pinned(buf, bytes);
+  if (!pinned && hipHostRegister(const_cast<void*>(buf), bytes, hipHostRegisterDefault) != hipSuccess) {
     (void)hipGetLastError();
     return MPI_ERR_OTHER;
   }
   Registration r;
   r.bytes = bytes;
+  r.pinned_here = !pinned;
   g_registered[key] = r;
   return MPI_SUCCESS;
 }
@@ -465,7 +489,7 @@ int MPI_Allreduce_FT_unregister(const void* buf) {
   auto it = g_registered.find(reinterpret_cast<uintptr_t>(buf));
   if (it == g_registered.end()) return MPI_ERR_ARG;
   if (it->second.in_use) return MPI_ERR_PENDING;  // a call is copying through it right now
-  (void)hipHostUnregister(reinterpret_cast<void*>(it->first));
+  unpin(*it);
   g_registered.erase(it);
   return MPI_SUCCESS;
 }
@@ -482,7 +506,7 @@ int MPI_Allreduce_FT_finalize(void) {
   for (Entry* e : live) MPI_Comm_delete_attr(e->owner, keyval);
   std::lock_guard<std::mutex> g(g_mu);
   if (g_keyval != MPI_KEYVAL_INVALID) MPI_Comm_free_keyval(&g_keyval);
-  for (auto& kv : g_registered) (void)hipHostUnregister(reinterpret_cast<void*>(kv.first));
+  for (auto& kv : g_registered) unpin(kv);
   g_registered.clear();
   return MPI_SUCCESS;
 }

@@ -27,7 +27,7 @@
 //                     at most T = 3 (HIP caps the queues at 32), else
 //                     refused (exit 2);
 //   --register-check  MPI_Allreduce_FT_register / _unregister semantics on a
-//                     scratch buffer (needs a GPU: hipHostRegister).
+//                     scratch buffer (needs a GPU).
 // --check is two-sided here: the reference only flags results that are too
 // LARGE (benchmark.cpp:201), so NaN/zero results pass there.
 // --exact (ring or single-stage topologies, no warmup): every element must
@@ -56,6 +56,33 @@
 #include <vector>
 
 #include "ftar_mpi.h"
+
+// n floats of host memory, page-locked from the start where `pinned` asks for it and a GPU is there
+// (hipHostMalloc: not every system can pin memory a program already has, so hipHostRegister of a
+// std::vector is refused on some), plain memory otherwise
+struct HostBuf {
+  float* p = nullptr;
+  size_t n = 0;
+  bool pinned = false;
+  HostBuf(size_t n_, bool want_pinned) : n(n_) {
+    const size_t bytes = (n ? n : 1) * sizeof(float);
+    void* q = nullptr;
+    if (want_pinned && hipHostMalloc(&q, bytes, hipHostMallocPortable) == hipSuccess) pinned = true;
+    else if (want_pinned) (void)hipGetLastError();
+    if (!pinned) q = malloc(bytes);
+    if (!q) abort();
+    p = static_cast<float*>(q);
+  }
+  ~HostBuf() {
+    if (pinned) (void)hipHostFree(p);
+    else free(p);
+  }
+  HostBuf(const HostBuf&) = delete;
+  HostBuf& operator=(const HostBuf&) = delete;
+  float* data() { return p; }
+  size_t size() const { return n; }
+  float& operator[](size_t i) { return p[i]; }
+};
 
 static void die(int rank, const std::string& msg) {
   fprintf(stderr, "[rank %d] %s\n", rank, msg.c_str());
@@ -142,7 +169,8 @@ int main(int argc, char** argv) {
   if (device && comm_type == "mpi") usage_error(rank, "--device needs --comm-type flextree");
   if (graph && !device) usage_error(rank, "--graph needs --device");
 
-  std::vector<float> data(data_len);
+  const bool want_registered = !device && comm_type == "flextree" && do_register && data_len;
+  HostBuf data(data_len, want_registered);
   const float base = 0.1f;
   for (size_t i = 0; i < data_len; ++i) data[i] = i * base;  // benchmark.cpp:125-129
 
@@ -152,7 +180,7 @@ int main(int argc, char** argv) {
   if (have_topo) ftar_topo_format(&topo, topo_s, sizeof topo_s);
 
   // the host buffer stays alive for the whole run: pin it once (RCCL-style user-buffer registration)
-  const bool registered = !device && comm_type == "flextree" && do_register && data_len &&
+  const bool registered = want_registered &&
                           MPI_Allreduce_FT_register(data.data(), data_len * sizeof(float)) == MPI_SUCCESS;
   float* dptr = nullptr;
   if (device) {
@@ -395,7 +423,8 @@ int main(int argc, char** argv) {
     }
   }
   if (register_check) {
-    std::vector<float> buf(1 << 20, 1.0f);
+    HostBuf buf(1 << 20, true);
+    for (size_t i = 0; i < buf.size(); ++i) buf[i] = 1.0f;
     const size_t bytes = buf.size() * sizeof(float);
     int bad_r = 0;
     bad_r += MPI_Allreduce_FT_register(buf.data(), bytes) != MPI_SUCCESS;

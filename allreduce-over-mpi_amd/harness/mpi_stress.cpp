@@ -133,19 +133,28 @@ int main(int argc, char** argv) {
       if (hipFree(a) != hipSuccess || hipFree(b) != hipSuccess) die(rank, "hipFree");
       ++device_calls;
     } else {
-      uint8_t* buf = in_place ? in.data() : out.data();
+      // registered buffers are allocated page-locked (hipHostMalloc): not every system can pin memory a
+      // program already has, and hipHostRegister of a std::vector is refused there
+      uint8_t *src = in.data(), *dst = out.data();
       if (reg && bytes) {
-        if (MPI_Allreduce_FT_register(in.data(), bytes) != MPI_SUCCESS) die(rank, std::string(what) + ": register");
-        if (!in_place && MPI_Allreduce_FT_register(out.data(), bytes) != MPI_SUCCESS)
+        if (hipHostMalloc(reinterpret_cast<void**>(&src), bytes, hipHostMallocPortable) != hipSuccess ||
+            (!in_place && hipHostMalloc(reinterpret_cast<void**>(&dst), bytes, hipHostMallocPortable) != hipSuccess))
+          die(rank, std::string(what) + ": hipHostMalloc");
+        memcpy(src, in.data(), bytes);
+        if (!in_place) memset(dst, 0x5a, bytes);
+        if (MPI_Allreduce_FT_register(src, bytes) != MPI_SUCCESS) die(rank, std::string(what) + ": register");
+        if (!in_place && MPI_Allreduce_FT_register(dst, bytes) != MPI_SUCCESS)
           die(rank, std::string(what) + ": register out");
         ++registered;
       }
-      rc = MPI_Allreduce_FT(in_place ? MPI_IN_PLACE : in.data(), buf, (int)n, t.mpi, op, comm);
-      if (reg && bytes) {
-        MPI_Allreduce_FT_unregister(in.data());
-        if (!in_place) MPI_Allreduce_FT_unregister(out.data());
-      }
+      uint8_t* buf = in_place ? src : dst;
+      rc = MPI_Allreduce_FT(in_place ? MPI_IN_PLACE : src, buf, (int)n, t.mpi, op, comm);
       got.assign(buf, buf + bytes);
+      if (reg && bytes) {
+        MPI_Allreduce_FT_unregister(src);
+        if (!in_place) MPI_Allreduce_FT_unregister(dst);
+        if (hipHostFree(src) != hipSuccess || (!in_place && hipHostFree(dst) != hipSuccess)) die(rank, "hipHostFree");
+      }
     }
     if (rc != MPI_SUCCESS) die(rank, std::string(what) + ": returned " + std::to_string(rc));
     if (got != want) {

@@ -644,7 +644,8 @@ ftar_status_t ftar_allreduce_host_group(const void* const* sendbufs, void* const
                                         ftar_dtype_t dtype, ftar_op_t op, const ftar_topo_t* topo,
                                         ftar_comm_t* comms, int nranks, void* const* streams);
 /* Co-scheduling of the fold with the transport: the reduce stream runs on
- * `cus` of the device's CUs (spread evenly; 0 = all, the default), so the
+ * `cus` of the device's CUs (every XCD its share, never fewer than one CU
+ * per XCD, i.e. 8 in all; 0 = all, the default), so the
  * comm stream's kernels (RCCL p2p, copies) always find free CUs while a
  * piece's fold runs (FTAR_REDUCE_CUS at init).  Same bits either way.
  * In-process (local) and host-bootstrapped communicators only: on an RCCL

@@ -51,6 +51,10 @@ int MPI_Allreduce_FT_comm(MPI_Comm comm, ftar_comm_t* out);
 
 /* Pin a host buffer for the copies of MPI_Allreduce_FT (hipHostRegister),
  * until MPI_Allreduce_FT_unregister; the caller keeps it alive meanwhile.
+ * A buffer allocated page-locked (hipHostMalloc) is pinned already and only
+ * recorded; where the system cannot pin memory a program already has (some
+ * virtual machines) any other buffer is refused with MPI_ERR_OTHER, so
+ * allocate it with hipHostMalloc there.
  * Calls on unregistered buffers copy pageable, unless FTAR_MPI_REGISTER=1
  * (pin every buffer passed in, at most FTAR_MPI_REGISTER_MAX = 4 kept, least
  * recently used evicted: the caller must not free such a buffer while it may
