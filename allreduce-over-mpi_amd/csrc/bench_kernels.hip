@@ -5,6 +5,7 @@
 // reduce_impl.h are instantiated here from the same templates; launch_gather (variant 90) and
 // launch_reduce (the nested-fold A/B) are the product's own, linked from libftar.so.
 #include "cast_impl.h"
+#include "half_impl.h"
 #include "mx_impl.h"
 #include "reduce_impl.h"
 
@@ -722,6 +723,171 @@ extern "C" ftar_status_t ftar_bench_sr_sweep(int e5m2, unsigned long long first,
   if (st == FTAR_SUCCESS && count) {
     if (e5m2) hipLaunchKernelGGL(sr_sweep_kernel<true>, dim3(4096), dim3(256), 0, nullptr, first, count, d_bad, d_ex);
     else hipLaunchKernelGGL(sr_sweep_kernel<false>, dim3(4096), dim3(256), 0, nullptr, first, count, d_bad, d_ex);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = FTAR_ERR_HIP;
+  }
+  if (st == FTAR_SUCCESS && (hipMemcpy(mismatches, d_bad, NB, hipMemcpyDeviceToHost) != hipSuccess ||
+                             hipMemcpy(examples, d_ex, NE, hipMemcpyDeviceToHost) != hipSuccess))
+    st = FTAR_ERR_HIP;
+  hip_ignore(hipFree(d_bad));
+  hip_ignore(hipFree(d_ex));
+  return st;
+}
+
+// ---------------------------------------------------------------------------
+// Stochastic rounding to bf16 / f16 (ftar_cast_half_sr, half_impl.h): the hooks of tests/test_gpu_half_sr.py,
+// tools/sr_sweep.py --half and tools/cast_rates.py --half.
+// ---------------------------------------------------------------------------
+// The production cast (same kernels, layout and narrowing) on an explicit array of words, words[i] for element i,
+// in place of the generator.  No amax.
+extern "C" ftar_status_t ftar_bench_cast_half_sr_words(const void* src, int src_dtype, void* dst, int dst_dtype,
+                                                       size_t count, const float* scale, const unsigned* words,
+                                                       void* stream) {
+  using namespace ftar;
+  if (!half_sr_pair((ftar_dtype_t)src_dtype, (ftar_dtype_t)dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!src || !dst || !words || !count) return FTAR_ERR_INVALID_ARG;
+  FTAR_CHECK_HIP((launch_half_sr_any<SrWords>(src, dst, (ftar_dtype_t)dst_dtype, count, scale, nullptr,
+                                              static_cast<hipStream_t>(stream), SrWords::Arg{words, count})));
+  return FTAR_SUCCESS;
+}
+
+// The candidates of the vector kernel through the generator (tools/cast_rates.py --half): layout 0 = lane-contiguous
+// 16-byte f32 loads with 8-byte stores, 1 = each lane owns one destination vector; u = destination vectors per lane
+// and pass (1, 2 or 4); mode 0 = the narrowing in integers, 1 = the instruction with the integer form beside it.
+extern "C" ftar_status_t ftar_debug_cast_half_variant(int layout, int u, int mode, const void* src, void* dst,
+                                                      int dst_dtype, size_t count, const float* scale,
+                                                      const unsigned long long* seed, unsigned long long offset,
+                                                      void* stream) {
+  using namespace ftar;
+  if (!half_sr_pair(FTAR_FLOAT32, (ftar_dtype_t)dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!src || !dst || !seed || !count) return FTAR_ERR_INVALID_ARG;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipError_t e = hipErrorInvalidValue;
+#define FTAR_HALF_VARIANT(L, U_, M)                                                                            \
+  if (layout == (L) && u == (U_) && mode == (M))                                                               \
+    e = launch_half_sr_any<SrGen, M, U_, L>(src, dst, (ftar_dtype_t)dst_dtype, count, scale, nullptr, s,       \
+                                            SrGen::Arg{seed, offset});
+  FTAR_HALF_VARIANT(kHalfWide, 1, kSrInt)
+  FTAR_HALF_VARIANT(kHalfWide, 2, kSrInt)
+  FTAR_HALF_VARIANT(kHalfWide, 4, kSrInt)
+  FTAR_HALF_VARIANT(kHalfOwn, 1, kSrInt)
+  FTAR_HALF_VARIANT(kHalfOwn, 2, kSrInt)
+  FTAR_HALF_VARIANT(kHalfWide, 1, kSrHw)
+  FTAR_HALF_VARIANT(kHalfWide, 2, kSrHw)
+  FTAR_HALF_VARIANT(kHalfWide, 4, kSrHw)
+  FTAR_HALF_VARIANT(kHalfOwn, 1, kSrHw)
+  FTAR_HALF_VARIANT(kHalfOwn, 2, kSrHw)
+#undef FTAR_HALF_VARIANT
+  if (e == hipErrorInvalidValue) return FTAR_ERR_INVALID_ARG;
+  FTAR_CHECK_HIP(e);
+  return FTAR_SUCCESS;
+}
+
+namespace ftar {
+namespace {
+// sr16 of ftar.h step by step as written there (e, ulp, lo, F, the carry), on the format's own parameters: what
+// SrH16 (its integer form, and the instructions) is held against.  *f_out: F.
+template <bool BF>
+__device__ unsigned sr16_contract(unsigned bits, unsigned u, unsigned* f_out) {
+  constexpr int M = BF ? 7 : 10, BIAS = BF ? 127 : 15, EMIN = 1 - BIAS;
+  constexpr unsigned INF = BF ? 0x7f80u : 0x7c00u;
+  const unsigned a = bits & 0x7fffffffu, sign = (bits >> 16) & 0x8000u;
+  *f_out = 0;
+  if (a > 0x7f800000u) return sign | INF | 1u;
+  if (a == 0x7f800000u) return sign | INF;
+  if (a == 0) return sign;
+  const int ee = (a >> 23) ? (int)(a >> 23) : 1;
+  const unsigned long long sig = (a & 0x7fffffu) | ((a >> 23) ? 0x800000u : 0u);   // a = sig * 2^(ee - 150)
+  const int e = ee - 127, q = (e > EMIN ? e : EMIN) - M;                            // ulp = 2^q
+  const int k = q - (ee - 150);                                                     // a / ulp = sig / 2^k, k >= 13
+  const unsigned long long lo = k < 64 ? sig >> k : 0, rem = k < 64 ? sig & ((1ull << k) - 1) : sig;
+  unsigned long long F;
+  if (k <= 32) F = rem << (32 - k);
+  else F = (k - 32) < 64 ? rem >> (k - 32) : 0;
+  *f_out = (unsigned)F;
+  const unsigned long long units = lo + (((unsigned long long)u + F) >> 32);
+  unsigned long long enc;
+  if (e < EMIN) enc = units;                                                         // subnormal range
+  else enc = ((unsigned long long)(e + BIAS) << M) + (units - (1u << M));
+  return sign | (unsigned)(enc < INF ? enc : INF);
+}
+template <bool BF>
+__device__ bool h16_bits_differ(unsigned got, unsigned want) {
+  constexpr unsigned INF = BF ? 0x7f80u : 0x7c00u;
+  const bool ng = (got & 0x7fffu) > INF, nw = (want & 0x7fffu) > INF;
+  return ng != nw || (!nw && got != want);
+}
+constexpr int kHalfSweepWords = 4;
+// modes: 0 the production narrowing (SrH16::pack in both halves and SrH16::narrow), 1 the bare instruction fed U
+// (both halves), 2 the bare instruction fed U >> (32 - d), d = 23 - m.  words: 0, 2^32 - 1, the input's threshold
+// 2^32 - F and 2^32 - F - 1.  bad[mode][word][fp32 exponent field], ex as in sr_sweep_kernel.
+template <bool BF>
+__global__ void __launch_bounds__(256) half_sr_sweep_kernel(unsigned long long first, unsigned long long count,
+                                                            unsigned long long* bad, unsigned* ex) {
+  using F = SrH16<BF>;
+  constexpr int SH = 32 - F::kDrop;
+  __shared__ unsigned bins[kSweepModes * kHalfSweepWords * 256];
+  for (int j = threadIdx.x; j < kSweepModes * kHalfSweepWords * 256; j += 256) bins[j] = 0;
+  __syncthreads();
+  const unsigned long long stride = (unsigned long long)gridDim.x * 256;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += stride) {
+    const unsigned b = (unsigned)(first + i), ebin = (b >> 23) & 0xffu;
+    const float p = __uint_as_float(b);
+    unsigned f;
+    sr16_contract<BF>(b, 0u, &f);
+    const unsigned w[kHalfSweepWords] = {0u, 0xffffffffu, 0u - f, 0u - f - 1u};
+    const u32x2 pk = F::template pack<kHalfSrMode>(f32x4{p, p, p, p}, u32x4{w[0], w[1], w[2], w[3]});
+    const u32x2 pr = F::template pack<kHalfSrMode>(f32x4{p, p, p, p}, u32x4{w[1], w[0], w[3], w[2]});
+#pragma unroll
+    for (int j = 0; j < kHalfSweepWords; ++j) {
+      unsigned dummy;
+      const unsigned want = sr16_contract<BF>(b, w[j], &dummy);
+      unsigned got[kSweepModes];
+      got[0] = ((j < 2 ? pk.x : pk.y) >> (16 * (j & 1))) & 0xffffu;
+      const unsigned other = ((j < 2 ? pr.x : pr.y) >> (16 * ((j & 1) ^ 1))) & 0xffffu, nar = F::template narrow<kHalfSrMode>(p, w[j]);
+      if (h16_bits_differ<BF>(other, want)) got[0] = 0x20000u | other;
+      if (h16_bits_differ<BF>(nar, want)) got[0] = 0x10000u | nar;
+      got[1] = F::template hw<0>(p, w[j], 0u) & 0xffffu;
+      if (h16_bits_differ<BF>(F::template hw<1>(p, w[j], 0u) >> 16, want)) got[1] = 0x20000u | (F::template hw<1>(p, w[j], 0u) >> 16);
+      got[2] = F::template hw<0>(p, w[j] >> SH, 0u) & 0xffffu;
+#pragma unroll
+      for (int m = 0; m < kSweepModes; ++m) {
+        if (got[m] > 0xffffu || h16_bits_differ<BF>(got[m], want)) {
+          atomicAdd(&bins[(m * kHalfSweepWords + j) * 256 + ebin], 1u);
+          unsigned* slot = ex + (m * 256 + ebin) * 4;
+          if (atomicCAS(slot, 0xffffffffu, b) == 0xffffffffu) {
+            slot[1] = w[j];
+            slot[2] = got[m];
+            slot[3] = want;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < kSweepModes * kHalfSweepWords * 256; j += 256)
+    if (bins[j]) atomicAdd(bad + j, (unsigned long long)bins[j]);
+}
+}  // namespace
+}  // namespace ftar
+
+// tools/sr_sweep.py --half's hook: ftar_bench_sr_sweep for the two 16-bit destinations (bf16 != 0: bf16, else f16).
+// mismatches: 3 x 4 x 256 counts, added to; examples: 3 x 256 x 4 words, as there.
+extern "C" ftar_status_t ftar_bench_half_sr_sweep(int bf16, unsigned long long first, unsigned long long count,
+                                                  unsigned long long* mismatches, unsigned* examples) {
+  using namespace ftar;
+  if (!mismatches || !examples || first + count > (1ull << 32)) return FTAR_ERR_INVALID_ARG;
+  constexpr size_t NB = (size_t)kSweepModes * kHalfSweepWords * 256 * sizeof(unsigned long long);
+  constexpr size_t NE = (size_t)kSweepModes * 256 * 4 * sizeof(unsigned);
+  unsigned long long* d_bad = nullptr;
+  unsigned* d_ex = nullptr;
+  ftar_status_t st = FTAR_SUCCESS;
+  if (hipMalloc(&d_bad, NB) != hipSuccess || hipMalloc(&d_ex, NE) != hipSuccess) st = FTAR_ERR_NO_MEMORY;
+  if (st == FTAR_SUCCESS && (hipMemcpy(d_bad, mismatches, NB, hipMemcpyHostToDevice) != hipSuccess ||
+                             hipMemcpy(d_ex, examples, NE, hipMemcpyHostToDevice) != hipSuccess))
+    st = FTAR_ERR_HIP;
+  if (st == FTAR_SUCCESS && count) {
+    if (bf16) hipLaunchKernelGGL(half_sr_sweep_kernel<true>, dim3(4096), dim3(256), 0, nullptr, first, count, d_bad, d_ex);
+    else hipLaunchKernelGGL(half_sr_sweep_kernel<false>, dim3(4096), dim3(256), 0, nullptr, first, count, d_bad, d_ex);
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) st = FTAR_ERR_HIP;
   }
   if (st == FTAR_SUCCESS && (hipMemcpy(mismatches, d_bad, NB, hipMemcpyDeviceToHost) != hipSuccess ||

@@ -279,6 +279,22 @@ ftar_status_t ftar_cast_scaled_sr(const void* src, ftar_dtype_t src_dtype, void*
                                      reinterpret_cast<unsigned*>(amax), static_cast<hipStream_t>(stream));
 }
 
+// f32 -> bf16 / f16 with stochastic rounding (half_impl.h): ftar_cast_scaled_sr's refusals in its order, all
+// before the memset.
+ftar_status_t ftar_cast_half_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                                size_t count, const float* scale, const uint64_t* seed, uint64_t offset,
+                                float* amax, void* stream) {
+  if (!ftar::cast_half_sr_pair_supported(src_dtype, dst_dtype)) return FTAR_ERR_UNSUPPORTED;
+  if (!seed || (reinterpret_cast<uintptr_t>(seed) & 7)) return FTAR_ERR_INVALID_ARG;
+  if ((reinterpret_cast<uintptr_t>(scale) & 3) || (reinterpret_cast<uintptr_t>(amax) & 3)) return FTAR_ERR_INVALID_ARG;
+  if (count && (!src || !dst)) return FTAR_ERR_INVALID_ARG;
+  if (amax) FTAR_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(float), static_cast<hipStream_t>(stream)));
+  if (count == 0) return FTAR_SUCCESS;
+  return ftar::launch_cast_half_sr(src, src_dtype, dst, dst_dtype, count, scale,
+                                   reinterpret_cast<const unsigned long long*>(seed), offset,
+                                   reinterpret_cast<unsigned*>(amax), static_cast<hipStream_t>(stream));
+}
+
 // The MX block-scaled casts (mx_kernels.hip): kernels only, so each call is the nodes of its kernels in a captured
 // graph.  The pair is checked first, then the mode and the headroom, then the pointers; count == 0 writes nothing.
 ftar_status_t ftar_mx_scales(const void* src, ftar_dtype_t src_dtype, ftar_dtype_t fp8_dtype, size_t count,

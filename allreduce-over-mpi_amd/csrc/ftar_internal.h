@@ -263,6 +263,12 @@ bool cast_sr_pair_supported(ftar_dtype_t src, ftar_dtype_t dst);
 ftar_status_t launch_cast_scaled_sr(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt,
                                     size_t count, const float* scale, const unsigned long long* seed,
                                     unsigned long long offset, unsigned* amax, hipStream_t stream);
+// ftar_cast_half_sr's (cast_kernels.hip, half_impl.h): f32 -> bf16 / f16 with sr16(p, U(*seed, offset + i)); any
+// other pair: FTAR_ERR_UNSUPPORTED before anything else.
+bool cast_half_sr_pair_supported(ftar_dtype_t src, ftar_dtype_t dst);
+ftar_status_t launch_cast_half_sr(const void* src, ftar_dtype_t src_dt, void* dst, ftar_dtype_t dst_dt, size_t count,
+                                  const float* scale, const unsigned long long* seed, unsigned long long offset,
+                                  unsigned* amax, hipStream_t stream);
 // The MX block-scaled casts' kernels (mx_kernels.hip; the contract: include/ftar.h): one E8M0 byte per 32 elements.
 // wide in {f32, bf16, f16} with f8 in {e4m3, e5m2}; any other pair: FTAR_ERR_UNSUPPORTED before anything else.
 // Kernels only: no memset, no host read.  given: the quantize reads scales[] instead of writing it.

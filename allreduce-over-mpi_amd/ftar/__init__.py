@@ -131,7 +131,8 @@ _lib.ftar_reduce_amax.argtypes = [ctypes.POINTER(_vp), _int, _vp, _sz, _int, cty
                                   _int, _vp, _vp]
 _lib.ftar_cast_scaled.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, _vp]
 _lib.ftar_cast_scaled_sr.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, ctypes.c_uint64, _vp, _vp]
-_lib.ftar_mx_scales.argtypes = [_vp, _int, _int, _sz, _int, _vp, _vp]
+_lib.ftar_cast_half_sr.argtypes = [_vp, _int, _vp, _int, _sz, _vp, _vp, ctypes.c_uint64, _vp, _vp]
+_lib.ftar_mx_scales.argtypes =[_vp, _int, _int, _sz, _int, _vp, _vp]
 _lib.ftar_mx_quantize.argtypes = [_vp, _int, _vp, _int, _sz, _int, _int, _vp, _vp]
 _lib.ftar_mx_quantize_sr.argtypes = [_vp, _int, _vp, _int, _sz, _int, _int, _vp, _vp, ctypes.c_uint64, _vp]
 _lib.ftar_mx_dequantize.argtypes = [_vp, _int, _vp, _vp, _int, _sz, _vp]
@@ -229,7 +230,7 @@ _bench_lib = None
 def bench_lib():
     """libftar_bench.so: the A/B kernel variants (ftar_debug_reduce_variant, ftar_debug_reduce_nested_lds) and
     kernel test hooks (ftar_debug_bf16_cvt_check, ftar_debug_f16_cvt_check, ftar_debug_f8_cvt_check,
-    ftar_bench_cast_sr_words, ftar_bench_mx_quantize_sr_words, ftar_bench_sr_sweep) that tools/kbench*.py and the tests load; kept out of the
+    ftar_bench_cast_sr_words, ftar_bench_cast_half_sr_words, ftar_bench_mx_quantize_sr_words, ftar_bench_sr_sweep) that tools/kbench*.py and the tests load; kept out of the
     product library, which holds only the kernels the engine dispatches."""
     global _bench_lib
     if _bench_lib is None:
@@ -423,6 +424,39 @@ def cast_scaled_tensor(src, dst, scale=None, amax=None, stream=None, rounding="n
         _one_elem(seed, "seed", src.device, torch.int64)
     cast_scaled(src, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), scale, amax, stream, rounding,
                 seed if stochastic else None, offset)
+    return dst
+
+
+# ---- f32 -> bf16 / f16 with stochastic rounding -----------------------------------------
+def cast_half_sr(src, dst, count, src_dtype, dst_dtype, seed, scale=None, offset=0, amax=None, stream=None):
+    """dst[i] = (src[i] * scale) rounded stochastically to bf16 or f16, enqueued on `stream` (ftar_cast_half_sr): f32
+    to bf16 / f16 only.  Each element goes to one of its two 16-bit neighbours with the expectation of the product,
+    decided by a 32-bit word that is a pure function of the 64-bit value at `seed` (device memory, 8-byte aligned: a
+    pointer or a 1-element int64 tensor) and of the global element index offset + i.  scale and amax as in
+    cast_scaled; no saturation (an overflow is inf).  A seed of None raises ValueError before any device work."""
+    if seed is None:
+        raise ValueError("cast_half_sr needs a seed in device memory")
+    _check(_lib.ftar_cast_half_sr(_ptr(src), _dt(src_dtype), _ptr(dst), _dt(dst_dtype), count, _ptr(scale), _ptr(seed),
+                                  int(offset) & 0xFFFFFFFFFFFFFFFF, _ptr(amax), _stream(stream)), "ftar_cast_half_sr")
+
+
+def cast_half_sr_tensor(src, dst, seed, scale=None, offset=0, amax=None, stream=None):
+    """cast_half_sr on two tensors: the dtypes and the count are the tensors' own.  ValueError unless both are
+    contiguous, of equal numel and on one device, scale / amax are 1-element fp32 tensors on that device and seed is
+    a 1-element int64 tensor there.  Returns dst."""
+    import torch
+    if src.numel() != dst.numel():
+        raise ValueError(f"src has {src.numel()} elements, dst {dst.numel()}")
+    if not src.is_contiguous() or not dst.is_contiguous():
+        raise ValueError("src and dst must be contiguous")
+    if src.device != dst.device:
+        raise ValueError(f"src is on {src.device}, dst on {dst.device}")
+    _one_f32(scale, "scale", src.device)
+    _one_f32(amax, "amax", src.device)
+    if seed is None:
+        raise ValueError("cast_half_sr_tensor needs a seed: a 1-element int64 tensor")
+    _one_elem(seed, "seed", src.device, torch.int64)
+    cast_half_sr(src, dst, src.numel(), _dt(str(src.dtype)), _dt(str(dst.dtype)), seed, scale, offset, amax, stream)
     return dst
 
 

@@ -40,6 +40,8 @@ mx_compress_hook (with MxCompressState) is the block-scaled (MX) form of that wi
 32 elements, agreed among the ranks in the same step by a MAX AllReduce of the bytes, so small layers of a bucket
 keep their bits and no step overflows the wire; no scale policy to run.  It takes rounding="stochastic" too
 (ftar_mx_quantize_sr), with Fp8CompressState's seed and offset.
+half_compress_hook (with HalfCompressState) reduces an f32 bucket on a bf16 / f16 wire, the cast to it stochastic
+(ftar_cast_half_sr) with the same seed and offset.
 
 The reference reduces MPI buffers (MPI_Allreduce_FT, mpi_mod.hpp:1723-1778); a DDP bucket is the same call on
 a device tensor, in place (`sendbuf = MPI_IN_PLACE`).
@@ -378,6 +380,91 @@ def mx_compress_hook(state, bucket):
     state.comm.allreduce(None, wire, n, f8, "avg", topo_=state.topo, lonely=state.lonely, stream=stream)
     ftar.mx_dequantize(wire, scales, t, n, f8, dt, stream=stream)
     torch.maximum(state._inf, (scales[:nb].max() == 255).to(torch.float32).reshape(1), out=state._inf)
+    state.calls += 1
+    fut = torch.futures.Future(devices=[t.device])
+    fut.set_result(t)
+    return fut
+
+
+# ---- the 16-bit wire ------------------------------------------------------------------------------------
+_HALF_WIRE = {"bf16": torch.bfloat16, "f16": torch.float16}
+
+
+class HalfCompressState:
+    """What half_compress_hook needs: the communicator, the wire format ("bf16" or "f16"), optionally a fixed
+    topology, and how the f32 bucket is rounded to the wire.  rounding="stochastic" (the default here: it is what
+    this hook is for) rounds each element to one of its two 16-bit neighbours with the expectation of the value
+    (ftar_cast_half_sr), so the error is zero-mean and averages down over ranks and steps where round-to-nearest to
+    bf16's 8 significant bits pushes every rank the same way; "nearest" is torch's cast.  The state keeps a grow-only
+    16-bit wire, `seed` (stochastic: a 1-element int64 device tensor derived once on the host from (seed, comm.rank)
+    through rank_seed), `offset` (a host-side count of the elements cast so far, never reset, so no two buckets share
+    a word; under graph capture it is baked into the captured kernel, as in Fp8CompressState) and `amax`, the running
+    maximum of the reduced wires' abs-max since the last reset_amax(); found_inf() and reset_amax() are HookState's.
+    No host synchronisation anywhere."""
+
+    def __init__(self, comm, fmt="bf16", topo=None, lonely=0, rounding="stochastic", seed=0):
+        if fmt not in _HALF_WIRE:
+            raise ValueError(f"fmt must be 'bf16' or 'f16', not {fmt!r}")
+        if rounding not in ftar.ROUNDINGS:
+            raise ValueError(f"rounding must be 'nearest' or 'stochastic', not {rounding!r}")
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError(f"seed must be an integer, not {seed!r}")
+        self.comm, self.fmt, self.topo, self.lonely = comm, fmt, topo, lonely
+        self.rounding, self.base_seed = rounding, seed
+        self.seed = None      # stochastic: the rank's device seed, created on the first bucket's device
+        self.offset = 0
+        self.amax = self._bucket_amax = self._wire = None
+        self.calls = 0
+
+    def _on(self, device, n):
+        if self.amax is None:
+            self.amax = torch.zeros(1, dtype=torch.float32, device=device)
+            self._bucket_amax = torch.zeros(1, dtype=torch.float32, device=device)
+            if self.rounding == "stochastic":
+                word = rank_seed(self.base_seed, getattr(self.comm, "rank", 0))
+                self.seed = torch.tensor([word - (1 << 64) if word >> 63 else word], dtype=torch.int64, device=device)
+        if self._wire is None or self._wire.numel() < n:
+            self._wire = torch.empty(n, dtype=_HALF_WIRE[self.fmt], device=device)
+        return self._wire[:n]
+
+    def reset_amax(self):
+        """Start a new running maximum (once per optimizer step, after the scaler has read found_inf())."""
+        if self.amax is not None:
+            self.amax.zero_()
+
+    def found_inf(self):
+        """A 1-element fp32 device tensor: 1.0 where `amax` is inf or NAN -- a bucket overflowed the wire at the cast
+        or in a fold, or held a NAN -- else 0.0; no host synchronisation."""
+        if self.amax is None:
+            raise RuntimeError("found_inf() before the first bucket")
+        return (~torch.isfinite(self.amax)).to(torch.float32)
+
+
+def half_compress_hook(state, bucket):
+    """DDP comm hook: an f32 bucket reduced on a bf16 / f16 wire, all on the stream the backward pass runs on, no host
+    synchronisation: (1) the bucket rounded to the wire format -- ftar_cast_half_sr on state.seed at the running
+    state.offset, or with state.rounding == "nearest" torch's wire.copy_(bucket); (2) the wire's in-place AllReduce
+    with op="avg" and amax (fp32 accumulate and one rounding in the one-round forms); (3) bucket.copy_(wire), an exact
+    widening; (4) state.amax = maximum(state.amax, this bucket's amax).  Returns a completed future, as
+    allreduce_hook does.  Nothing saturates: an f16 overflow at the cast or in a fold is inf on the wire and reaches
+    found_inf().  A bucket that is not float32, or not contiguous, raises ValueError before any device work."""
+    t = bucket.buffer()
+    if t.dtype != torch.float32:
+        raise ValueError(f"half_compress_hook takes float32 buckets, not {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError("half_compress_hook needs a contiguous bucket")
+    n = t.numel()
+    stream = torch.cuda.current_stream(t.device)
+    wire = state._on(t.device, n)
+    a = state._bucket_amax
+    if state.rounding == "stochastic":
+        ftar.cast_half_sr(t, wire, n, "f32", state.fmt, state.seed, offset=state.offset, stream=stream)
+        state.offset += n
+    else:
+        wire.copy_(t.view(-1))
+    state.comm.allreduce(None, wire, n, state.fmt, "avg", topo_=state.topo, lonely=state.lonely, stream=stream, amax=a)
+    t.view(-1).copy_(wire)
+    torch.maximum(state.amax, a, out=state.amax)
     state.calls += 1
     fut = torch.futures.Future(devices=[t.device])
     fut.set_result(t)

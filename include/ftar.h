@@ -81,6 +81,7 @@ typedef enum {
  *   every other dtype (f64 included: its amax does not fit the word) and every other op is refused.
  *   cast (ftar_cast_scaled): f32 bf16 f16 -> f8e4m3 f8e5m2 and back, times a device scale; every other pair is refused.
  *   stochastic cast (ftar_cast_scaled_sr): f32 bf16 f16 -> f8e4m3 f8e5m2 only; the way back and every other pair is refused.
+ *   stochastic 16-bit cast (ftar_cast_half_sr): f32 -> bf16 f16 only; every other pair is refused.
  *   MX casts (ftar_mx_scales, ftar_mx_quantize: f32 bf16 f16 -> f8e4m3 f8e5m2; ftar_mx_dequantize: the way back); every other pair is refused.
  *   stochastic MX quantize (ftar_mx_quantize_sr): f32 bf16 f16 -> f8e4m3 f8e5m2, both modes; every other pair is refused.
  *
@@ -188,6 +189,25 @@ typedef enum {
  * a NULL seed, a seed not 8-byte aligned, a scale or amax not 4-byte aligned, or a NULL src or dst with
  * count > 0 returns FTAR_ERR_INVALID_ARG; every refusal comes before any device work and leaves dst and *amax
  * untouched.  count == 0 succeeds, and a non-NULL amax then holds +0.0.
+ *
+ * Stochastic rounding to the 16-bit floats (ftar_cast_half_sr): the sending end of a bf16 / f16 wire.  f32 -> bf16
+ * and f32 -> f16; every other pair returns FTAR_ERR_UNSUPPORTED, and that check comes first.  Per element
+ * dst[i] = sr16(mul_rn_f32(src[i], r), U(*seed, offset + i)): r, the multiply, U, seed and offset are exactly those
+ * of the stochastic-rounding paragraph above, and sr16 is its sr_dst with the destination's parameters: bf16 m = 7,
+ * emin = -126; f16 m = 10, emin = -14.  In the normal range d = 23 - m bits are dropped (16 / 13) and the magnitude's
+ * encoding goes up by one iff ((bits & (2^d - 1)) << (32 - d)) + U >= 2^32; the carry runs into the next encoding and
+ * past the largest finite one into inf.  bf16 shares fp32's exponent range, so d = 16 over the whole finite range,
+ * fp32 subnormals included, and a magnitude above bf16's largest finite value becomes +-inf with probability frac.
+ * f16: below 2^-14 the ulp stays 2^-24, F = floor(frac x 2^32) and bits under 2^-32 ulp are dropped; a magnitude in
+ * (65504, 65536) becomes +-inf with probability frac and from 65536 on always.  Both: +-0 stays +-0, the sign is kept
+ * when a non-zero value rounds to zero, +-inf stays +-inf, a NaN stays a NaN of unspecified pattern for every U, a
+ * representable product is stored unchanged for every U, U = 0 truncates toward zero, and nothing saturates.  amax is
+ * ftar_cast_scaled's word for dst.  Refusals in ftar_cast_scaled_sr's order after the pair: a NULL seed or one not
+ * 8-byte aligned (at count == 0 too), a scale or amax not 4-byte aligned, a NULL src or dst with count > 0 return
+ * FTAR_ERR_INVALID_ARG; every refusal comes before any device work and leaves dst and *amax untouched.  count == 0
+ * succeeds.  Casting [0, n) in one call stores the bits of casting [0, a) and [a, n) with offset = a, for any a;
+ * pointers need only their element's alignment (a pair whose 16-byte alignments do not fit runs an element-wise
+ * kernel that stores the same bits).
  *
  * MX block-scaled casts (ftar_mx_scales, ftar_mx_quantize, ftar_mx_dequantize): an fp8 wire with one power-of-two
  * scale byte (OCP E8M0) per block of FTAR_MX_BLOCK = 32 elements.  Block b of a call covers the call's indices
@@ -334,6 +354,13 @@ ftar_status_t ftar_cast_scaled(const void* src, ftar_dtype_t src_dtype, void* ds
 ftar_status_t ftar_cast_scaled_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
                                   size_t count, const float* scale, const uint64_t* seed, uint64_t offset,
                                   float* amax, void* stream);
+/* f32 to bf16 / f16 with stochastic rounding (extension; the 16-bit stochastic-rounding paragraph above):
+ * dst[i] = sr16(src[i] x *scale, U(*seed, offset + i)), one streaming kernel on `stream`.  scale, seed, offset,
+ * amax, count == 0, pointer alignment and graph capture (a 4-byte memset and one kernel with amax, the kernel alone
+ * without) as for ftar_cast_scaled_sr. */
+ftar_status_t ftar_cast_half_sr(const void* src, ftar_dtype_t src_dtype, void* dst, ftar_dtype_t dst_dtype,
+                                size_t count, const float* scale, const uint64_t* seed, uint64_t offset,
+                                float* amax, void* stream);
 /* MX block-scaled casts (extension; the MX paragraph above): fp8 elements plus one E8M0 scale byte per 32. */
 #define FTAR_MX_BLOCK 32
 typedef enum { FTAR_MX_COMPUTE = 0, FTAR_MX_GIVEN = 1 } ftar_mx_mode_t;

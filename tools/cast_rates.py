@@ -12,13 +12,18 @@ written, median of interleaved rounds with the slowest and fastest round next to
   f32>f8e4m3@L.U      layout candidate L (0 lane-owned vectors, 1 the same staged through LDS, 2 lane-contiguous
                       wide vectors with 4- / 8-byte fp8 accesses) at U vectors per lane and pass, through
                       libftar_bench.so's ftar_debug_cast_variant (--layouts)
+  f32>bf16:sr         ftar_cast_half_sr (--half: f32 to bf16 and f16 with stochastic rounding; 384 MiB moved), and
+  f32>bf16:sr@L.U.M   its candidates through ftar_debug_cast_half_variant: layout L (0 lane-contiguous 16-byte f32
+                      loads with 8-byte stores, 1 lane-owned destination vectors), U destination vectors per lane and
+                      pass, narrowing M (0 in integers, 1 the instruction with the integer form beside it); --half also
+                      runs f32>f8e4m3+sr and copy:384 in the same rounds
   copy:320            launch_copy (ftar.reduce, k = 1, u8) of 160 MiB: 320 MiB moved, an f32 pair's total;
                       copy:384 is a 16-bit pair's
   ...#2               any label again under a name of its own: the tool's own spread between two runs of one
                       kernel, the margin for "as fast as the copy"
 
 Random bytes on both sides, so lanes hold NaN and inf too: the instructions do not care.
-python tools/cast_rates.py [--pairs f32>f8e4m3,...] [--layouts] [--amax] [--sr] [--rounds 5] [--reps 8]"""
+python tools/cast_rates.py [--pairs f32>f8e4m3,...] [--layouts] [--amax] [--sr] [--half] [--rounds 5] [--reps 8]"""
 import argparse
 import ctypes
 import json
@@ -40,6 +45,7 @@ ap.add_argument("--layouts", action="store_true", help="also every layout candid
 ap.add_argument("--layout-pairs", default="f32>f8e4m3,bf16>f8e4m3,f8e4m3>f32,f8e4m3>bf16")
 ap.add_argument("--amax", action="store_true", help="also every pair with the amax word")
 ap.add_argument("--sr", action="store_true", help="also every quantize pair with stochastic rounding")
+ap.add_argument("--half", action="store_true", help="also f32 -> bf16 / f16 with stochastic rounding, every candidate")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--reps", type=int, default=8)
 a = ap.parse_args()
@@ -53,6 +59,10 @@ seed = torch.full((1,), 0x5EED, dtype=torch.int64, device="cuda")
 hook = ftar.bench_lib().ftar_debug_cast_variant
 hook.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
                  ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+half_hook = ftar.bench_lib().ftar_debug_cast_half_variant
+half_hook.argtypes = [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
+HALF_VARIANTS = [(lay, u, m) for m in (0, 1) for lay, u in ((0, 1), (0, 2), (0, 4), (1, 1), (1, 2))]
 
 
 def moved(pair):
@@ -68,6 +78,18 @@ def make(label):
         total = int(base[5:]) << 20
         return (lambda i: ftar.reduce([bufs[i % S][0]], bufs[i % S][1], total // 2, "u8", "sum", stream=stream)), total
     pair, _, var = base.partition("@")
+    if pair.endswith(":sr"):
+        d, n = pair[:-3].split(">")[1], NB // 4
+        if not var:
+            return (lambda i: ftar.cast_half_sr(bufs[i % S][0], bufs[i % S][1], n, "f32", d, seed, scale=scale, offset=i * n,
+                                                stream=stream)), 6 * n
+        lay, u, m = (int(x) for x in var.split("."))
+
+        def launch_half(i):
+            st = half_hook(lay, u, m, bufs[i % S][0].data_ptr(), bufs[i % S][1].data_ptr(), ftar.DTYPE[d], n,
+                           scale.data_ptr(), seed.data_ptr(), i * n, stream.cuda_stream)
+            assert st == 0, (label, st, ftar.last_error())
+        return launch_half, 6 * n
     pair, plus, _ = pair.partition("+")   # _: "amax" or "sr"
     s, d = pair.split(">")
     n, total = moved(pair)
@@ -94,7 +116,10 @@ sr_pairs = [p for p in pairs if p.split(">")[1] in F8] if a.sr else []
 labels += [p + "+sr" for p in sr_pairs]
 if a.layouts:
     labels += [f"{p}@{lay}.{u}" for p in a.layout_pairs.split(",") for lay, u in VARIANTS]
-for mib in sorted({moved(p)[1] >> 20 for p in pairs}):
+if a.half:
+    labels += [f"f32>{d}:sr{v}" for d in ("bf16", "f16") for v in [""] + [f"@{x}.{y}.{z}" for x, y, z in HALF_VARIANTS]]
+    labels += [lb for lb in ("f32>f8e4m3+sr",) if lb not in labels]
+for mib in sorted({moved(p)[1] >> 20 for p in pairs} | ({384} if a.half else set())):
     labels += [f"copy:{mib}", f"copy:{mib}#2"]
 runs = {lb: make(lb) for lb in labels}
 res = {}

@@ -12,7 +12,10 @@ word that rounds up) and 2^32 - F - 1 (the largest that rounds down).  Three mod
 Mismatches are counted per fp32 exponent field (0 .. 255) and printed as ranges of fields, with one example each
 (input bits, word, got, want).  The production mode must show none; the bare modes show where the instruction
 alone equals the contract, which is what SrFmt's use of it stands on (csrc/cast_impl.h).
-python tools/sr_sweep.py [--chunks 16]"""
+--half sweeps the narrowing to bf16 and f16 instead (ftar_cast_half_sr; ftar_bench_half_sr_sweep): four words per input
+(0, 2^32 - 1, 2^32 - F, 2^32 - F - 1), production = SrH16::pack in both halves and SrH16::narrow, bare = v_cvt_sr_bf16_f32
+/ v_cvt_sr_f16_f32 in both halves (csrc/half_impl.h).
+python tools/sr_sweep.py [--half] [--chunks 16]"""
 import argparse
 import ctypes
 import json
@@ -28,12 +31,15 @@ import ftar  # noqa: E402
 MODES, WORDS = ("production", "bare", "bare>>"), ("0", "1", "2^31", "2^32-1", "2^32-F", "2^32-F-1")
 ap = argparse.ArgumentParser()
 ap.add_argument("--chunks", type=int, default=16, help="launches per format (progress is printed after each)")
+ap.add_argument("--half", action="store_true", help="the 16-bit destinations (bf16, f16) instead of the fp8 ones")
 a = ap.parse_args()
-hook = ftar.bench_lib().ftar_bench_sr_sweep
+hook = ftar.bench_lib().ftar_bench_half_sr_sweep if a.half else ftar.bench_lib().ftar_bench_sr_sweep
+if a.half:
+    WORDS = ("0", "2^32-1", "2^32-F", "2^32-F-1")
 hook.argtypes = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
 bad_total = 0
-for e5m2, name in ((0, "f8e4m3"), (1, "f8e5m2")):
-    bad = np.zeros((3, 6, 256), np.uint64)
+for e5m2, name in ((1, "bf16"), (0, "f16")) if a.half else ((0, "f8e4m3"), (1, "f8e5m2")):
+    bad = np.zeros((3, len(WORDS), 256), np.uint64)
     ex = np.full((3, 256, 4), 0xFFFFFFFF, np.uint32)
     step = (1 << 32) // a.chunks
     for c in range(a.chunks):
